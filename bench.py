@@ -2,13 +2,17 @@
 """bench.py — throughput of the HIP DNA-LLM hot path (BASELINE.json's metric: GRPO training-step samples/sec).
 
     python bench.py --gpus N --steps K --warmup W            # N > 1 self-launches one process per GPU (RCCL)
+    python bench.py --gpus 1 --steps K --warmup W --full     # + phase breakdown, one-stream profile, secondary legs, HF-on-GPU and CPU baselines
+    python bench.py --steps K --dump-outputs DIR             # + DIR/<name>.npy: what the last timed step computed (see dump_outputs)
     python bench.py --mode sft                               # BASELINE config 2 (train_dna_qwen.py SFT step), secondary line
     python bench.py --eos-uniform 64 256                     # SURVEY §8d straggler run (rollout lengths U[64, 256])
     python bench.py --prompts-per-gpu 2                      # secondary lines: sh_reason.sh's per_device_train_batch_size
     BENCH_DRYRUN=1 python bench.py --gpus 2                  # launcher rehearsal without GPUs: gloo + kernel-source emulator + toy dims
 
-The default run (N = 1) also times two SECONDARY legs after the headline steps and before the CPU leg, printed as sub-objects of
-the same JSON line: `sft` (BASELINE config 2, train_dna_qwen.py:179-213) and `straggler` (EOS drawn at U[64, 256]).
+A plain run sets up, warms up, times the K steps and prints the JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, the
+workload, and the rooflines measured with HIP events inside the timed steps).  Everything that takes steps or processes of its own runs
+under --full only: with it the default run (N = 1) also times the SECONDARY legs after the headline steps and before the CPU leg, printed as
+sub-objects of the same JSON line: `sft` (BASELINE config 2, train_dna_qwen.py:179-213), `straggler` (EOS drawn at U[64, 256]), ...
 
 GRPO "step" (default, cfg-3 of SURVEY §8d) = one full GRPO step on one batch of synthetic DNA+prompt input per GPU:
 NT-500M encoder + Qwen3-1.7B, 1 unique prompt x G=8 rollouts per GPU, prompt P = 2180 (2 DNA sequences x 1024 NT
@@ -19,9 +23,10 @@ reward functions reason.py enables by default -> device; a synthetic id -> text 
 reward all-gather + group advantages, gradient all-reduce, AdamW with grad clip 1.0.
 SFT "step" (cfg-2) = forward (full-row lm_head logits + shifted CE on the last 64 positions) / backward / all-reduce /
 AdamW over B=8 distinct samples of the same shape.
-Inputs are resident in HBM before the timed region.  value = samples per second over all ranks.
+Inputs are resident in HBM before the timed region.  value = samples per second over all ranks.  Every step of the headline leg starts from
+the trainable state that set-up left (from_initial_state), so that a run computes the same numbers every time it is made.
 
-The JSON line also carries
+The JSON line also carries (cpu_baseline, gpu_baseline_hf, value_reference_semantics and the secondary legs: under --full)
   roofline        — the MFMA-bound kernel family: gemm_ring_kernel (256x256 LDS-ring tiles, most of the time) + gemm_glds_kernel
                     (256x128, under-filled grids and the row-split remainders) = every projection / lm_head GEMM of the prefill,
                     log-prob and backward passes that fills the chip: algorithmic FLOPs 2*M*N*(K+K2) of exactly those API calls /
@@ -613,6 +618,66 @@ def make_sft_leg(model, dims: Dims, R: int, rank: int, dev):
     return runner, step, B
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+DUMP_SAMPLE = 2 * 2 ** 20       # elements kept of a tensor larger than that (seeded index sample, the same in every run)
+
+
+def dump_outputs(path: str, out, runner, model, rank: int, dev):
+    """--dump-outputs: what the last timed step handed to its caller, as <name>.npy files (float32; integers and float64 as float64):
+    the tensors of step()'s result, the scored rollout the GRPO step was computed from (the runner keeps it for the passes that reuse
+    it), and the trainable parameters with their gradients as the step left them — a fixed seeded sample of DUMP_SAMPLE elements each.
+    Inputs, weights and sampler seeds are fixed by the arguments, so two builds can be compared file by file."""
+    import numpy as np
+    import torch
+    if dev.type == "cuda":
+        torch.cuda.synchronize()
+    named = {"step_" + k: v for k, v in (out or {}).items()}
+    buffered = getattr(runner, "_buffered_inputs", None)
+    if buffered:
+        ga = max(1, runner.cfg.gradient_accumulation_steps)
+        inputs = buffered[(runner._step - 1) % ga]
+        for k in ("completion_ids", "completion_mask", "old_per_token_logps", "ref_per_token_logps", "advantages", "rewards_per_func"):
+            named["rollout_" + k] = inputs.get(k)
+    named["trainable_params"], named["trainable_grads"] = model.arena.params, model.arena.grads
+    os.makedirs(path, exist_ok=True)
+    suffix = ".npy" if rank == 0 else ".rank%d.npy" % rank
+    total = 0
+    for name, t in sorted(named.items()):
+        if not torch.is_tensor(t):
+            continue
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(20240229)).sort().values
+            t = t[idx.to(t.device)]
+        wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+        a = t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+        total += a.nbytes
+        assert total <= DUMP_LIMIT_BYTES, "--dump-outputs: more than %d bytes" % DUMP_LIMIT_BYTES
+        np.save(os.path.join(path, name + suffix), a)
+
+
+def from_initial_state(arena, step):
+    """-> step(i, timing) that first puts the trainable state back to what set-up left: master parameters, zeroed AdamW moments, optimiser
+    step 0, bf16 images re-packed (three device copies / fills and the pack kernel, ~0.2 ms of a 410 ms step, issued on the launch stream
+    inside the timed region).  The weight-gradient kernels add their partial sums with fp32 atomics, in an order that differs from run to
+    run by a rounding; carried through AdamW and the bf16 packing over several steps that rounding reaches the sampler and the rollouts
+    of two runs part company.  With every step starting from the same state, every step's inputs — the last timed step's, which
+    --dump-outputs writes, among them — are the same in every run, and the step's results differ by that rounding alone.  Each step is
+    still one whole training step (rollout, reference and policy passes, backward, reduction, clip, AdamW, pack); the per-step sampler
+    and dropout seeds advance as before."""
+    initial = arena.params.detach().clone()
+
+    def step_from_initial_state(i, timing=False):
+        arena.params.copy_(initial)
+        if arena.exp_avg is not None:
+            arena.exp_avg.zero_()
+            arena.exp_avg_sq.zero_()
+        arena.step_count = 0
+        arena.pack()
+        return step(i, timing=timing)
+    return step_from_initial_state
+
+
 TIMED_DIAG: dict = {}      # diagnostics of the LAST timed_steps call (read by main() right after the headline's): host load, allocator
 
 
@@ -678,6 +743,15 @@ def main():
                          "record blocks delay their reuse — and a hipMalloc inside the timed region costs 8 ms per step on a quiet host, far more "
                          "on a loaded one: timed_region_diagnostics.allocator_* in the line shows whether any happened)")
     ap.add_argument("--mode", choices=["grpo", "sft"], default="grpo")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the instrumented phase-breakdown steps, the "
+                         "per-bucket and one-stream profile steps, the secondary legs (straggler, rollout_fp8, unshared_policy, prompts_per_gpu_2, "
+                         "sft, qwen3_4b), the oracle on this GPU (gpu_baseline_hf) and on the host cores (cpu_baseline); the --no-* options "
+                         "below take single parts out of it.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32 / float64): the tensors "
+                         "step() returned, the rollout it was computed from, and a fixed seeded sample of the trainable parameters and their "
+                         "gradients as that step left them (ranks > 0 write <name>.rank<r>.npy)")
     ap.add_argument("--no-one-stream-profile", action="store_true", help="skip the extra untimed step that profiles the GEMM family with every chain on one stream")
     ap.add_argument("--prompts-per-gpu", type=int, default=1, help="distinct prompts per GPU (x G=8 rollouts each); headline = 1")
     ap.add_argument("--eos-uniform", type=int, nargs=2, metavar=("LO", "HI"), default=None,
@@ -714,6 +788,8 @@ def main():
     ap.add_argument("--no-gpu-baseline-hf", action="store_true", help="skip the `gpu_baseline_hf` leg (the oracle on this GPU through stock PyTorch-ROCm)")
     ap.add_argument("--gpu-baseline-hf-only", action="store_true", help="internal: run the oracle-on-GPU timing leg and print its JSON")
     args = ap.parse_args()
+    if not args.full:        # a plain run does what the headline figure needs and nothing beside it
+        args.no_one_stream_profile = args.no_secondary = args.no_cpu_baseline = args.no_gpu_baseline_hf = True
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline(args.mode)), flush=True)
         return
@@ -780,6 +856,7 @@ def main():
         runner, step, samples_per_step = make_sft_leg(model, dims, R, rank, dev)
     else:
         runner, step, samples_per_step = make_grpo_leg(model, dims, R, Cn, rank, dev, args, args.eos_uniform, nsteps)
+    step = from_initial_state(model.arena, step)
 
     def before_timed():
         # the objects built so far (model, fixtures, the 152 k-entry id -> text table) leave the collector's generations, so a full
@@ -807,14 +884,17 @@ def main():
             loop_ev = {"ms": sum(ms_l) / len(ms_l), "steps": sum(st_l) / len(st_l), "rollouts": len(ms_l)}
     if hasattr(runner, "loop_events"):
         runner.loop_events = None
-    # phase breakdown (extra, untimed, instrumented steps: the first one lets the allocator see the serialised path's buffers — a fresh
-    # hipMalloc inside a measured phase has been seen to cost 100 ms on a loaded host —, the second one is reported)
-    step(args.warmup + args.steps, timing=True)
-    step(args.warmup + args.steps, timing=True)
+    if args.dump_outputs:                         # before any further step moves the parameters on
+        dump_outputs(args.dump_outputs, out, runner, model, rank, dev)
+    # --full: phase breakdown (extra, untimed, instrumented steps: the first one lets the allocator see the serialised path's buffers — a
+    # fresh hipMalloc inside a measured phase has been seen to cost 100 ms on a loaded host —, the second one is reported)
+    if args.full:
+        step(args.warmup + args.steps, timing=True)
+        step(args.warmup + args.steps, timing=True)
     # N > 1 (or the one-rank RCCL rehearsal): one more untimed, overlapped step with per-bucket stamps — when each gradient bucket was
     # handed to the collective and when the step had waited for it, against the end of the backward (trainer.bucket_report)
     dp_buckets = None
-    if getattr(runner, "dp", False) and dev.type == "cuda" and hasattr(runner, "bucket_report"):
+    if args.full and getattr(runner, "dp", False) and dev.type == "cuda" and hasattr(runner, "bucket_report"):
         runner.trace_buckets = True
         step(args.warmup + args.steps + 2)
         dp_buckets = runner.bucket_report()
@@ -976,8 +1056,10 @@ def main():
             "executed_tflop_per_step": ex / 1e12,
             "step_tflops_executed": ex / 1e12 / (elapsed / args.steps),
             "step_frac_of_mfma_peak_executed": ex / 1e12 / (elapsed / args.steps) / PEAK_BF16_TFLOPS,
-            "phases_ms": {k: round(v, 2) for k, v in headline_timers.items()},
+            **({"phases_ms": {k: round(v, 2) for k, v in headline_timers.items()}} if args.full else {}),
             "loss": loss,
+            "step_state": "every step starts from the trainable state that set-up left (parameters, zeroed AdamW moments, optimiser step 0): "
+                          "the timed steps compute the same numbers in every run, up to the rounding of the fp32 atomic gradient sums",
             "timed_region_diagnostics": headline_diag,
             **({"dp_buckets": dp_buckets} if dp_buckets else {}),
             "hbm_reserved_gib": (torch.cuda.max_memory_reserved(dev) / 2.0 ** 30) if dev.type == "cuda" else None,   # peak of the caching allocator over all legs run so far (of 288)
@@ -1013,7 +1095,8 @@ def main():
             if dec is not None and dec["share_of_step_ms"] > gemm_ms:
                 line["roofline"] = dict(dec, dominant_by_time="token loop %.0f ms of the %.0f ms step; MFMA GEMM family %.0f ms (roofline_mfma)"
                                         % (dec["share_of_step_ms"], step_ms, gemm_ms))
-            line["rollout_phases_ms"] = {k: round(v, 2) for k, v in headline_rollout.items() if isinstance(v, float)}
+            if args.full:
+                line["rollout_phases_ms"] = {k: round(v, 2) for k, v in headline_rollout.items() if isinstance(v, float)}
             line["rollout_issue"] = {"mode": "graph" if getattr(model.text_model.engine, "_rollout_use_graph", False) else "eager",
                                      "probe_host_vs_device_ms_per_token": getattr(model.text_model.engine, "_rollout_probe_ms", None)}
             # the reference's accounting (every row re-runs its full prompt and the encoder): an upper bound on executed work

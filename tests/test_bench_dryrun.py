@@ -71,7 +71,7 @@ def test_eight_rank_self_launch_prints_one_line(emu_lib_path):
 
 
 def test_single_process_line_carries_the_secondary_legs(emu_lib_path):
-    r = _run(["--steps", "1", "--warmup", "1", "--secondary-steps", "1", "--completion-len", "4"])
+    r = _run(["--full", "--steps", "1", "--warmup", "1", "--secondary-steps", "1", "--completion-len", "4"])
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     (d,) = _json_lines(r.stdout)
     assert d["n_gpus"] == 1 and "cpu_baseline" not in d                  # the CPU leg is skipped in a dry run
@@ -81,6 +81,44 @@ def test_single_process_line_carries_the_secondary_legs(emu_lib_path):
     assert "gemm_ring_kernel" in d["roofline_mfma"]["kernel"]
     assert d["roofline"]["bound"] in ("hbm", "mfma") and "frac" in d["roofline"]       # = whichever family is dominant by time
     assert d["unshared_policy"]["value"] > 0
+
+
+def test_plain_run_is_lean_and_dumps_what_it_computed(emu_lib_path, tmp_path):
+    """without --full: set-up, warm-up, the timed steps, the line — no instrumented steps, no secondary legs, no baselines; --steps sets
+    the number of timed steps; --dump-outputs writes the last timed step's results as float32 / float64 .npy files; two runs with the
+    same arguments compute the same numbers"""
+    import numpy as np
+
+    def run(tag, steps, warmup):
+        out = tmp_path / tag
+        r = _run(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--completion-len", "4", "--dump-outputs", str(out)])
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+        (d,) = _json_lines(r.stdout)
+        return d, {f: np.load(out / f) for f in sorted(os.listdir(out))}
+
+    d, dump = run("k3", 3, 1)
+    for k in REQUIRED:
+        assert k in d, k
+    assert d["steps"] == 3 and len(d["timed_region_diagnostics"]["host_ms_inside_step_calls"]) == 3
+    assert d["unit"] == "samples/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert abs(d["value"] - d["config"]["global_batch"] / (d["ms_per_step"] / 1000.0)) < 1e-6 * d["value"]
+    for k in ("sft", "straggler", "unshared_policy", "cpu_baseline", "gpu_baseline_hf", "phases_ms", "rollout_phases_ms"):
+        assert k not in d, k
+    assert {"step_loss_t.npy", "rollout_completion_ids.npy", "trainable_params.npy", "trainable_grads.npy"} <= set(dump)
+    assert sum(v.nbytes for v in dump.values()) <= 64 * 2 ** 20
+    for f, v in dump.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), f
+    assert dump["rollout_completion_ids.npy"].size == 2 * 4 and np.abs(dump["trainable_grads.npy"]).max() > 0
+    assert float(dump["step_loss_t.npy"][0]) == d["loss"]
+    # a second run with the same arguments: every step starts from the state that set-up left, so the last timed step's inputs are
+    # identical (the same rollout ids); the only run-to-run freedom is the order of the fp32 atomic adds of the split weight-gradient
+    # kernels — at most a few hundred addends of 2^-24 relative rounding each, bounded here by 2^-16 of the array's largest magnitude
+    d2, dump2 = run("again", 3, 1)
+    assert set(dump2) == set(dump) and d2["loss"] == d["loss"]
+    assert np.array_equal(dump["rollout_completion_ids.npy"], dump2["rollout_completion_ids.npy"])
+    for f in dump:
+        assert dump[f].shape == dump2[f].shape, f
+        np.testing.assert_allclose(dump[f], dump2[f], rtol=0.0, atol=2.0 ** -16 * float(np.abs(dump[f]).max()), err_msg=f)
 
 
 def test_world_size_mismatch_is_refused():

@@ -8,10 +8,10 @@ tag=${1:-r5_x}
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 out=$R/gpurun_out/evidence_$tag; mkdir -p $out
 cd /tmp; export TMPDIR=/tmp
-BENCH="python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --no-one-stream-profile --no-gpu-baseline-hf"
+BENCH="python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --no-one-stream-profile --no-gpu-baseline-hf"
 if [ "$PMC_ONLY" = "1" ]; then :      # only the counter passes (the bench line and the kernel stats of this state exist already)
-elif [ "$NOCPU" = "1" ]; then timeout 300 python $R/bench.py --no-cpu-baseline --steps 5 2>/dev/null | tail -1 > $out/${tag}_bench.json
-else timeout 1200 python $R/bench.py --steps 5 2>$out/${tag}_bench.err | tail -1 > $out/${tag}_bench.json; fi
+elif [ "$NOCPU" = "1" ]; then timeout 300 python $R/bench.py --full --no-cpu-baseline --steps 5 2>/dev/null | tail -1 > $out/${tag}_bench.json
+else timeout 1200 python $R/bench.py --full --steps 5 2>$out/${tag}_bench.err | tail -1 > $out/${tag}_bench.json; fi
 [ "$PMC_ONLY" = "1" ] || { rm -rf /tmp/ev_stats; timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/ev_stats -o r --output-format csv -- $BENCH > /tmp/ev_stats.log 2>&1
 f=$(find /tmp/ev_stats -name "*kernel_stats.csv" | head -1)
 { echo "# rocprofv3 --kernel-trace --stats --output-format csv -- $BENCH   (MI355X, $tag; 4 GRPO steps in the trace: warm-up, timed, two instrumented)"; cat $f; } > $out/${tag}_bench_kernel_stats.csv; }

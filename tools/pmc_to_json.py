@@ -13,7 +13,7 @@ def pick(rs, counter, key):
 h = hashlib.sha256()
 for f in ("k_gemm.hip", "bra_device.h"):
     h.update(open(os.path.join(R, "bioreason_amd", "csrc", f), "rb").read())
-res = {"kernel_source_sha": h.hexdigest()[:16], "command": "bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-secondary (the timed configuration; GRPO steps traced: see steps_in_trace)",
+res = {"kernel_source_sha": h.hexdigest()[:16], "command": "bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-secondary (the timed configuration; GRPO steps traced: see steps_in_trace)",
        "fetch_correction": 2.0, "steps_in_trace": NSTEPS, "kernels": {}}
 tot_b, tot_n = 0.0, 0
 for key in ("gemm_ring_kernel<0", "gemm_glds_kernel<0", "gemm_w4_kernel<0"):
