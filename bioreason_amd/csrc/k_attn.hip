@@ -1051,9 +1051,11 @@ static int g_attn_legacy_order = 0;
 static std::atomic<int> g_attn_legacy_order{0};
 #endif
 
-// the tile loaders address one (batch, head) slice with 32-bit element offsets built by a 24-bit multiply (load_rows / load_trans)
+// the tile loaders address one (batch, head) slice with 32-bit offsets built by a 24-bit multiply: load_rows / load_trans by the
+// stride in elements, the pipelined kernels (k_attn4.hip, k_attn4b.hip) by the stride in BYTES — so the stride stays below 2^23
+// elements (2^24 bytes) and the slice below 2^31 elements (2^32 bytes)
 static bool attn_fit32(long rows, long stride) {
-    return stride >= 0 && stride < (1L << 24) && rows < (1L << 24) && rows * stride < (1L << 31);
+    return stride >= 0 && stride < (1L << 23) && rows < (1L << 24) && rows * stride < (1L << 31);
 }
 
 static int attn_check(int B, int Hq, int Hkv, int Sq, int Sk, int hd) {

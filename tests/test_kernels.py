@@ -3,6 +3,9 @@
 Each test runs on the CPU kernel-source emulator (`backend == cpu`, part of `-m "not gpu"`) and on the real
 gfx950 library (`-m gpu`).  Inputs are bf16; tolerances are those of one bf16 rounding of the output
 (rel Frobenius <= 4e-3) unless the op is exact.
+
+Attention (prefill / training): the global bounds here are the coarse check; tests/test_attn_rowwise.py holds every output row
+against a float64 reference and its own rounding bound, at adversarial values, strided layouts and the step's own shapes.
 """
 import math
 
