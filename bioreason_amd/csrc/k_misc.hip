@@ -323,6 +323,10 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, fl
         if (c < 1.f) clip *= c;
     }
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        // the moving averages in the order written: under -ffast-math the compiler turns b m + (1 - b) g into g + b (m - g), which
+        // takes the small (1 - b2) g^2 out of a difference of two terms of size g^2 and leaves v with a relative error of
+        // 2^-24 / (1 - b2) = 6e-5 while v << g^2 (the first steps) instead of 2^-24
+#pragma clang fp reassociate(off)
         if (mask && !mask[i]) continue;
         const float gi = g[i] * clip;
         float pi = p[i];
@@ -542,7 +546,8 @@ extern "C" int bra_adamw(float* p, const float* g, float* m, float* v, const voi
                          float grad_scale, void* stream) {
     if (n == 0) return 0;
     if (!p || !g || !m || !v || step < 1) return BRA_ERR_ARG;
-    const float bc1 = 1.f - powf(b1, (float)step), bc2 = 1.f - powf(b2, (float)step);
+    // in double: b2^step is close to 1 for the first steps, and an fp32 power leaves 1 - b2^step with a relative error of 1e-5 there
+    const float bc1 = (float)(1.0 - pow((double)b1, (double)step)), bc2 = (float)(1.0 - pow((double)b2, (double)step));
     BRA_LAUNCH(adamw_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, p, g, m, v, (const uint8_t*)mask, n, lr, b1, b2, eps, wd, bc1, bc2,
                sumsq, max_norm, grad_scale);
     return BRA_LAUNCH_STATUS();
