@@ -17,7 +17,7 @@ namespace bra {
 struct DropCfg {
     uint32_t thr16;        // drop when the 15-bit field is < thr16 (name kept: the field is bits 1..15 of a 16-bit half)
     float inv_keep;        // 1 / (1 - p)
-    uint32_t seed[4];      // one stream per 32-column rank block (= per target module of a fused projection)
+    uint32_t seed[4];      // one stream per target module of a fused projection (rank 32: = per 32-column rank block)
 };
 
 __host__ __device__ inline uint32_t drop_threshold(float p) {

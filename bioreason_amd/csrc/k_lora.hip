@@ -1,12 +1,23 @@
 // k_lora.hip — the LoRA branch under training-mode dropout (PEFT: y += (alpha/r) * B(A(dropout(x))), lora_dropout = 0.05,
 // train_dna_qwen.py:155-167, reason.py:266,376-388).  PEFT gives every target module its own nn.Dropout, so the q / k / v
 // (and gate / up) adapters that share an input x see INDEPENDENT masks; the fused projections here therefore carry one
-// mask stream per 32-column rank block.  Masks are never stored: keep(seed, m, k) is a counter-based hash of the element
-// index, recomputed wherever the masked operand is needed —
+// mask stream per TARGET: target j owns rank columns [j r, (j + 1) r) of the group (engine.LoraGroup) and uses seed[j].
+// Masks are never stored: keep(seed, m, k) is a counter-based hash of the element index, recomputed wherever the masked
+// operand is needed —
 //   lora_down_drop   t[m, r]   = s * sum_k keep_j(m,k)/(1-p) x[m,k] A[r,k]            (forward, replaces the x A^T GEMM)
 //   lora_up_drop     dxl[m, k] = sum_j keep_j(m,k)/(1-p) sum_{r in j} dts[m,r] A[r,k]  (backward, the branch's input gradient)
 //   wgrad_tn (DROP)  dA[r, k] += sum_m dts[m,r] keep_j(m,k)/(1-p) x[m,k]               (k_wgrad.hip)
-// with j = r / 32.  torch's dropout scales in fp32 and rounds once to bf16; so does drop_apply8.
+// with j = column / r.  torch's dropout scales in fp32 and rounds once to bf16; so does drop_apply8.
+// The MFMA tile is 32 rank columns wide, so the adapter rank r (template parameter TR) decides how targets meet tiles:
+//   r = 32      one target = one 32-column block (the bench's shape; the entry points without _r, bit for bit as before)
+//   r = 64, 128 a target spans r / 32 blocks: its masked operand is built ONCE and feeds all of its MFMAs (the hash is the
+//               bound of these kernels, bra_dropout.h — never one hash per block)
+//   r = 8, 16   32 / r targets share a block: each gets its own masked operand and its own MFMA, with the other targets'
+//               rank rows (down, wgrad) or k elements (up) of the second operand zeroed in registers — the products they
+//               would add are exact zeros, so the block keeps ONE accumulator
+// The bra_*_r entry points carry (r, targets) and expect the LoraGroup layout R = ceil(targets r / 64) 64; groups wider than
+// 128 columns (r = 64 x 3, r = 128 x 2 / 3) are walked in slices of <= 128 columns by the launchers (down, wgrad: LDS and
+// accumulators do not fit more), each slice with the seeds of its own targets.
 #include "bra_device.h"
 #include "bra_api_internal.h"
 #include "bra_dropout.h"
@@ -31,8 +42,11 @@ struct LoraDownArgs {
 // carries 8 KB of x + 8 NL KB of A per workgroup, twice what the two-wave form had in flight.
 // RB = rank blocks of the (padded) output, NL <= RB of them live: both compile-time, so that no branch sits between the
 // accumulators and their MFMAs (a run-time block count moved them between AGPRs and VGPRs around every K step)
-template <int RB, int NL>
+// TR = adapter rank of a target, NT = targets in this launch (seed[0 .. NT)); TR = 32: NT = NL, one target per block
+template <int RB, int NL, int TR = 32, int NT = NL>
 __global__ __launch_bounds__(256) void lora_down_drop_kernel(LoraDownArgs g) {
+    static_assert(TR == 8 || TR == 16 || TR == 32 || TR == 64 || TR == 128, "adapter ranks with dropout");
+    static_assert(NL == (NT * TR + 31) / 32 && NL <= RB && NT <= 4, "live blocks = the blocks the targets cover");
     constexpr int KS = 128, XP = KS + 8;
     constexpr int XS_ELEMS = 2 * 32 * XP, AS_ELEMS = 2 * 32 * NL * XP;
     constexpr int RED_BYTES = 3 * NL * 64 * 16 * 4, STAGE_BYTES = (XS_ELEMS + AS_ELEMS) * 2;
@@ -96,11 +110,32 @@ __global__ __launch_bounds__(256) void lora_down_drop_kernel(LoraDownArgs g) {
             const int kk = 2 * wave + k2;
             const u32x4 xf = ld16(&xs[buf * 32 * XP + lrow * XP + 16 * kk + 8 * h]);
             const uint32_t e0 = (uint32_t)mrow * (uint32_t)g.K + (uint32_t)(KS * s + 16 * kk + 8 * h);
+            if constexpr (TR == 32) {
 #pragma unroll
-            for (int rb = 0; rb < NL; ++rb) {
-                const u32x4 af = drop_apply8(xf, g.d.seed[rb], e0, g.d.thr16, g.d.inv_keep);
-                const u32x4 bf = ld16(&as[buf * 32 * NL * XP + (32 * rb + lrow) * XP + 16 * kk + 8 * h]);
-                acc[rb] = mfma_32x32x16(af, bf, acc[rb]);
+                for (int rb = 0; rb < NL; ++rb) {
+                    const u32x4 af = drop_apply8(xf, g.d.seed[rb], e0, g.d.thr16, g.d.inv_keep);
+                    const u32x4 bf = ld16(&as[buf * 32 * NL * XP + (32 * rb + lrow) * XP + 16 * kk + 8 * h]);
+                    acc[rb] = mfma_32x32x16(af, bf, acc[rb]);
+                }
+            } else if constexpr (TR > 32) {
+#pragma unroll
+                for (int jt = 0; jt < NT; ++jt) {                // one masked fragment per target, TR / 32 MFMAs with it
+                    const u32x4 af = drop_apply8(xf, g.d.seed[jt], e0, g.d.thr16, g.d.inv_keep);
+#pragma unroll
+                    for (int b = 0; b < TR / 32; ++b) {
+                        const int rb = jt * (TR / 32) + b;
+                        const u32x4 bf = ld16(&as[buf * 32 * NL * XP + (32 * rb + lrow) * XP + 16 * kk + 8 * h]);
+                        acc[rb] = mfma_32x32x16(af, bf, acc[rb]);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int jt = 0; jt < NT; ++jt) {                // the block's other targets' rows of A are zeroed: this MFMA adds
+                    const int rb = jt * TR / 32;                 // exact zeros to their columns of the block's accumulator
+                    const u32x4 af = drop_apply8(xf, g.d.seed[jt], e0, g.d.thr16, g.d.inv_keep);
+                    const u32x4 bf = ld16(&as[buf * 32 * NL * XP + (32 * rb + lrow) * XP + 16 * kk + 8 * h]);
+                    acc[rb] = mfma_32x32x16(af, lrow / TR == jt % (32 / TR) ? bf : zero4, acc[rb]);
+                }
             }
         }
         if (s + 1 < s_hi) commit(buf ^ 1, s + 1);
@@ -165,18 +200,21 @@ struct LoraUpArgs {
     int nb_live;                    // rank blocks that belong to a target module (padding blocks contribute nothing)
 };
 
-// wave = 32 rows of dts, walks 32-column tiles of the output; rank-32 product per target, masked, summed over targets
-template <int RB, int NL>
+// wave = 32 rows of dts, walks 32-column tiles of the output; rank-TR product per target, masked, summed over targets.
+// The rank is the MFMA's k dimension here (16 per MFMA, 8 consecutive per lane half): a target's TR / 16 MFMAs run into one
+// accumulator before the mask select; TR = 8: a lane half holds exactly one target's 8 columns of a k16 chunk, the other half
+// is zeroed.  NC = live k16 chunks of the whole group (no slicing here: the sum over targets stays in fp32 registers)
+template <int RB, int NL, int TR = 32, int NT = NL>
 __global__ __launch_bounds__(256) void lora_up_drop_kernel(LoraUpArgs g) {
+    constexpr int NC = TR == 32 ? 2 * NL : (NT * TR + 15) / 16;
+    const u32x4 zero4 = {0u, 0u, 0u, 0u};
     const int lane = lane_id(), wave = (int)threadIdx.x >> 6, h = lane >> 5;
     const int m_base = ((int)blockIdx.x * 4 + wave) * 32;
     if (m_base >= g.M) return;
     int mr = m_base + (lane & 31); mr = mr < g.M ? mr : g.M - 1;
-    u32x4 df[NL][2];
+    u32x4 df[NC];                                              // chunk c = rank columns [16 c, 16 c + 16)
 #pragma unroll
-    for (int rb = 0; rb < NL; ++rb)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) df[rb][c] = ld16(g.dts + (long)mr * g.ldd + 32 * rb + 16 * c + 8 * h);
+    for (int c = 0; c < NC; ++c) df[c] = ld16(g.dts + (long)mr * g.ldd + 16 * c + 8 * h);
     uint32_t rowbase[8];                                       // m * K of the 8 rows this lane hashes (see below)
     {
         const uint32_t odd0 = (uint32_t)lane & 1u;             // column parity = lane parity (k0 is a multiple of 32)
@@ -195,11 +233,9 @@ __global__ __launch_bounds__(256) void lora_up_drop_kernel(LoraUpArgs g) {
     for (int k0 = k_lo; k0 < k_hi; k0 += 32) {
         const int kc = k0 + (lane & 31);
         const int kr = kc < g.K ? kc : g.K - 1;
-        u32x4 af[NL][2];
+        u32x4 af[NC];
 #pragma unroll
-        for (int rb = 0; rb < NL; ++rb)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) af[rb][c] = ld16(g.AT + (long)kr * g.ldat + 32 * rb + 16 * c + 8 * h);
+        for (int c = 0; c < NC; ++c) af[c] = ld16(g.AT + (long)kr * g.ldat + 16 * c + 8 * h);
         float o[16];
 #pragma unroll
         for (int q = 0; q < 16; ++q) o[q] = 0.f;
@@ -207,12 +243,16 @@ __global__ __launch_bounds__(256) void lora_up_drop_kernel(LoraUpArgs g) {
         const uint32_t odd = (uint32_t)kr & 1u;
         const uint32_t fsh = odd ? 17u : 1u;                   // this column's 15-bit field inside a pair hash
 #pragma unroll
-        for (int rb = 0; rb < NL; ++rb) {
+        for (int rb = 0; rb < NT; ++rb) {                      // rb = target
             f32x16 acc;
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-            acc = mfma_32x32x16(df[rb][0], af[rb][0], acc);
-            acc = mfma_32x32x16(df[rb][1], af[rb][1], acc);
+            if constexpr (TR >= 16) {
+#pragma unroll
+                for (int c = rb * (TR / 16); c < (rb + 1) * (TR / 16); ++c) acc = mfma_32x32x16(df[c], af[c], acc);
+            } else {
+                acc = mfma_32x32x16(h == rb % 2 ? df[rb / 2] : zero4, af[rb / 2], acc);
+            }
             uint32_t hh[16];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -329,6 +369,65 @@ static int lora_down_launch(const void* x, long ldx, const void* A, long lda, vo
     return BRA_LAUNCH_STATUS();
 }
 
+// (r, targets) of the _r entry points: the ranks with a masked kernel, in the LoraGroup layout
+static bool lora_rank_ok(int r, int nt, int R) {
+    return (r == 8 || r == 16 || r == 32 || r == 64 || r == 128) && nt >= 1 && nt <= 3 && R == (nt * r + 63) / 64 * 64;
+}
+
+static int lora_down_launch_r(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R, float alpha, float p,
+                              const unsigned* seeds, int r, int nt, float* part, int ksplit, void* stream) {
+    if (M == 0) return 0;
+    if (!x || !A || !t || M < 0 || K <= 0 || K % 8 || ldx % 8 || lda % 8 || !lora_rank_ok(r, nt, R)) return BRA_ERR_ARG;
+    if (!(p >= 0.f && p < 1.f) || (long)M * K >= (1l << 32)) return BRA_ERR_ARG;
+    const int nstep = (K + 127) / 128;
+    const int per = part ? (nstep + ksplit - 1) / ksplit : nstep;
+    const int ny = part ? (nstep + per - 1) / per : 1;
+    const dim3 grid((M + 31) / 32, ny);
+    bra_stream_t st = (bra_stream_t)stream;
+    // slices of <= 128 rank columns (r >= 64: whole targets, R = targets * r; r < 32: R = 64, one slice)
+    for (int c0 = 0; c0 < R; c0 += 128) {
+        const int Rs = R - c0 < 128 ? R - c0 : 128;
+        const int j0 = r >= 64 ? c0 / r : 0, nts = r >= 64 ? Rs / r : nt;
+        float* const ps = part ? part + (long)ksplit * M * c0 : nullptr;
+        bf16_t* const ts = (bf16_t*)t + c0;
+        LoraDownArgs g = {(const bf16_t*)x, ldx, (const bf16_t*)A + (long)c0 * lda, lda, ts, ldt, M, K, Rs, alpha,
+                          make_cfg(p, seeds[j0], nts > 1 ? seeds[j0 + 1] : 0u, nts > 2 ? seeds[j0 + 2] : 0u, 0u), (nts * r + 31) / 32, per, ps};
+#define BRA_LDR(RB_, NL_, TR_, NT_) BRA_LAUNCH((lora_down_drop_kernel<RB_, NL_, TR_, NT_>), grid, dim3(256), 0, st, g)
+        if (r == 8) { if (nts == 1) BRA_LDR(2, 1, 8, 1); else if (nts == 2) BRA_LDR(2, 1, 8, 2); else BRA_LDR(2, 1, 8, 3); }
+        else if (r == 16) { if (nts == 1) BRA_LDR(2, 1, 16, 1); else if (nts == 2) BRA_LDR(2, 1, 16, 2); else BRA_LDR(2, 2, 16, 3); }
+        else if (r == 64) { if (Rs == 64) BRA_LDR(2, 2, 64, 1); else BRA_LDR(4, 4, 64, 2); }
+        else BRA_LDR(4, 4, 128, 1);
+#undef BRA_LDR
+        if (part) {
+            const long MR = (long)M * Rs;
+            BRA_LAUNCH(lora_partial_reduce_kernel, dim3((unsigned)((MR / 4 + 255) / 256)), dim3(256), 0, st, (const float*)ps, ny, MR, Rs, alpha,
+                       ts, ldt);
+        }
+    }
+    return BRA_LAUNCH_STATUS();
+}
+
+// the same three kernels for adapter rank r = 8 / 16 / 32 / 64 / 128 with `nt` <= 3 targets: target j = rank columns
+// [j r, (j + 1) r), mask stream s_j; R = ceil(nt r / 64) 64.  r = 32 is the form above, through the same instantiations
+extern "C" int bra_lora_down_drop_r(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R,
+                                    float alpha, float p, unsigned s0, unsigned s1, unsigned s2, int r, int nt, void* stream) {
+    if (r == 32 && lora_rank_ok(r, nt, R)) return bra_lora_down_drop(x, ldx, A, lda, t, ldt, M, K, R, alpha, p, s0, s1, s2, 0u, nt, stream);
+    const unsigned seeds[3] = {s0, s1, s2};
+    return lora_down_launch_r(x, ldx, A, lda, t, ldt, M, K, R, alpha, p, seeds, r, nt, nullptr, 1, stream);
+}
+
+// part: [ksplit, M, R] floats
+extern "C" int bra_lora_down_drop_splitk_r(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R,
+                                           float alpha, float p, unsigned s0, unsigned s1, unsigned s2, int r, int nt, float* part,
+                                           int ksplit, void* stream) {
+    if (r == 32 && lora_rank_ok(r, nt, R))
+        return bra_lora_down_drop_splitk(x, ldx, A, lda, t, ldt, M, K, R, alpha, p, s0, s1, s2, 0u, nt, part, ksplit, stream);
+    const unsigned seeds[3] = {s0, s1, s2};
+    if (ksplit <= 1) return lora_down_launch_r(x, ldx, A, lda, t, ldt, M, K, R, alpha, p, seeds, r, nt, nullptr, 1, stream);
+    if (!part || ksplit > (K + 127) / 128 || ldt % 4) return BRA_ERR_ARG;
+    return lora_down_launch_r(x, ldx, A, lda, t, ldt, M, K, R, alpha, p, seeds, r, nt, part, ksplit, stream);
+}
+
 extern "C" int bra_lora_up_drop(const void* dts, long ldd, const void* AT, long ldat, void* out, long ldo, int M, int K, int R,
                                 float p, unsigned s0, unsigned s1, unsigned s2, unsigned s3, int nb_live, void* stream) {
     if (M == 0) return 0;
@@ -347,6 +446,32 @@ extern "C" int bra_lora_up_drop(const void* dts, long ldd, const void* AT, long 
     else if (R == 64) { if (nb_live == 1) BRA_LU(2, 1); else BRA_LU(2, 2); }
     else { if (nb_live == 3) BRA_LU(4, 3); else BRA_LU(4, 4); }        // (padding blocks hold zeros: treating them as live is exact, only slower)
 #undef BRA_LU
+    return BRA_LAUNCH_STATUS();
+}
+
+extern "C" int bra_lora_up_drop_r(const void* dts, long ldd, const void* AT, long ldat, void* out, long ldo, int M, int K, int R,
+                                  float p, unsigned s0, unsigned s1, unsigned s2, int r, int nt, void* stream) {
+    if (r == 32 && lora_rank_ok(r, nt, R)) return bra_lora_up_drop(dts, ldd, AT, ldat, out, ldo, M, K, R, p, s0, s1, s2, 0u, nt, stream);
+    if (M == 0) return 0;
+    if (!dts || !AT || !out || M < 0 || K <= 0 || ldd % 8 || ldat % 8 || !lora_rank_ok(r, nt, R)) return BRA_ERR_ARG;
+    if (!(p >= 0.f && p < 1.f) || (long)M * K >= (1l << 32)) return BRA_ERR_ARG;
+    const int mblk = (M + 127) / 128;
+    int splits = (1024 + mblk - 1) / mblk;
+    int k_chunk = ((K + splits - 1) / splits + 31) / 32 * 32;
+    k_chunk = k_chunk < 128 ? 128 : k_chunk;
+    LoraUpArgs g = {(const bf16_t*)dts, ldd, (const bf16_t*)AT, ldat, (bf16_t*)out, ldo, M, K, R, k_chunk, make_cfg(p, s0, s1, s2, 0u),
+                    (nt * r + 31) / 32};
+    const dim3 grid(mblk, (K + k_chunk - 1) / k_chunk);
+    bra_stream_t st = (bra_stream_t)stream;
+    // the whole group in one launch, whatever its width: only dts / A fragments grow with it (8 registers per 32 columns each)
+#define BRA_LUR(TR_, NT_) BRA_LAUNCH((lora_up_drop_kernel<(NT_ * TR_ + 63) / 64 * 2, (NT_ * TR_ + 31) / 32, TR_, NT_>), grid, dim3(256), 0, st, g)
+#define BRA_LUR3(TR_) do { if (nt == 1) BRA_LUR(TR_, 1); else if (nt == 2) BRA_LUR(TR_, 2); else BRA_LUR(TR_, 3); } while (0)
+    if (r == 8) BRA_LUR3(8);
+    else if (r == 16) BRA_LUR3(16);
+    else if (r == 64) BRA_LUR3(64);
+    else BRA_LUR3(128);
+#undef BRA_LUR3
+#undef BRA_LUR
     return BRA_LAUNCH_STATUS();
 }
 

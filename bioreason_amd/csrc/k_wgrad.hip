@@ -1,5 +1,6 @@
 // k_wgrad.hip — low-rank weight gradients straight from row-major activations.
-//   C[n, r] += alpha * sum_m Y[m, n] * T[m, r]            Y [M, N] bf16 (large), T [M, R] bf16 (R = 32, 64 or 128)
+//   C[n, r] += alpha * sum_m Y[m, n] * T[m, r]            Y [M, N] bf16 (large), T [M, R] bf16 (R = 32 or a multiple of 64;
+//                                                          more than 128 columns: one launch per slice of <= 128)
 // These are autograd's gradients of PEFT's lora_B (Y = dy, T = s * x A^T) and lora_A (Y = x, T = s * dy B, written
 // transposed), train_dna_qwen.py:155-167 / reason.py:376-388.  The contraction runs over the token index m, which is the
 // SLOW index of both operands, so neither is "K-contiguous" as an MFMA fragment wants.  The first version transposed
@@ -20,7 +21,7 @@ struct WgradArgs {
     int M, N, R;
     int m_chunk;                    // rows of m per workgroup (multiple of 32)
     float alpha;
-    DropCfg d;                      // DROP: Y is used as keep_rb(m, n) / (1 - p) * Y[m, n], one mask stream per rank block
+    DropCfg d;                      // DROP: Y is used as keep_j(m, n) / (1 - p) * Y[m, n], one mask stream per target j (TR columns of T)
     int nb_live;                    // DROP: rank blocks that belong to a target module (the rest is padding: skipped)
 };
 
@@ -31,12 +32,16 @@ constexpr int WG_YP = 128 + 8;      // LDS row pitch of the Y tile (elements): 2
 // sits between the accumulators and their MFMAs
 // RM: C is [R, N] (dA: n is its contiguous index) — the accumulator lanes then run along n.  Compile-time: as a run-time select
 // between mfma(bf, af) and mfma(af, bf) it cost 16 accumulator-register moves and a full MFMA drain behind every MFMA
-template <int RB, int DROP, int NL = RB, int RM = 0>
+// TR / NT (DROP): adapter rank of a target and targets in this launch; target j = columns [j TR, (j + 1) TR) of T, seed[j].
+// TR = 32: one target per block (NT = NL).  TR > 32: the blocks of a target share its masked copy.  TR < 32: the targets of a
+// block each multiply their own masked copy with the block's T fragment, the other targets' columns of it zeroed in registers
+template <int RB, int DROP, int NL = RB, int RM = 0, int TR = 32, int NT = NL>
 __global__ __launch_bounds__(256) void wgrad_tn_kernel(WgradArgs g) {
-    // plain: the Y tile double-buffered.  DROP: one MASKED copy of the tile per live rank block (the mask is applied where a
+    static_assert(!DROP || (NL == (NT * TR + 31) / 32 && NT <= 4), "live blocks = the blocks the targets cover");
+    // plain: the Y tile double-buffered.  DROP: one MASKED copy of the tile per target (the mask is applied where a
     // thread holds 8 consecutive elements of a row — one hash per element pair, no exchange between lanes — and the fragment
-    // reads below then differ per rank block only by their base address), single-buffered with two barriers per step
-    constexpr int NYS = DROP ? NL : 2;
+    // reads below then differ per target only by their base address), single-buffered with two barriers per step
+    constexpr int NYS = DROP ? NT : 2;
     __shared__ bf16_t ys[NYS][32 * WG_YP];
     constexpr int WG_TP = 32 * RB + 8, TPT = RB >= 2 ? RB / 2 : 1;      // T tile pitch; 16-byte chunks per thread
     __shared__ bf16_t ts[2][32 * WG_TP];
@@ -81,8 +86,8 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(WgradArgs g) {
             for (int i = 0; i < 2; ++i) {
                 const uint32_t e0 = (uint32_t)(m_lo + 32 * s + yr + 16 * i) * (uint32_t)g.N + (uint32_t)(n0 + yc);
 #pragma unroll
-                for (int rb = 0; rb < NL; ++rb)
-                    st16(&ys[rb][(yr + 16 * i) * WG_YP + yc], drop_apply8(yv[i], g.d.seed[rb], e0, g.d.thr16, g.d.inv_keep));
+                for (int jt = 0; jt < NT; ++jt)
+                    st16(&ys[jt][(yr + 16 * i) * WG_YP + yc], drop_apply8(yv[i], g.d.seed[jt], e0, g.d.thr16, g.d.inv_keep));
             }
         } else {
             st16(&ys[buf][yr * WG_YP + yc], yv[0]);
@@ -123,22 +128,51 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(WgradArgs g) {
                 for (int j = 0; j < 4; ++j)
                     af0[j] = (uint32_t)ys[buf][(mb + 2 * j) * WG_YP + ncol] | ((uint32_t)ys[buf][(mb + 2 * j + 1) * WG_YP + ncol] << 16);
             }
+            auto y_frag = [&](int jt) {                          // DROP: this lane's fragment of target jt's masked copy
+                u32x4 f;
 #pragma unroll
-            for (int rb = 0; rb < NL; ++rb) {                    // (a padding block's T columns are zero: nothing to add)
-                u32x4 af = af0;
-                if (DROP) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        af[j] = (uint32_t)ys[rb][(mb + 2 * j) * WG_YP + ncol] | ((uint32_t)ys[rb][(mb + 2 * j + 1) * WG_YP + ncol] << 16);
-                }
+                for (int j = 0; j < 4; ++j)
+                    f[j] = (uint32_t)ys[jt][(mb + 2 * j) * WG_YP + ncol] | ((uint32_t)ys[jt][(mb + 2 * j + 1) * WG_YP + ncol] << 16);
+                return f;
+            };
+            auto t_frag = [&](int rb) {
                 const int rc = rb * 32 + (lane & 31);
                 uint32_t b[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     b[j] = (uint32_t)ts[buf][(mb + 2 * j) * WG_TP + rc] | ((uint32_t)ts[buf][(mb + 2 * j + 1) * WG_TP + rc] << 16);
                 const u32x4 bf = {b[0], b[1], b[2], b[3]};
-                // lanes of the accumulator run along the operand given SECOND: the contiguous index of C goes there
-                acc[rb] = r_major ? mfma_32x32x16(bf, af, acc[rb]) : mfma_32x32x16(af, bf, acc[rb]);
+                return bf;
+            };
+            if constexpr (!DROP || TR == 32) {
+#pragma unroll
+                for (int rb = 0; rb < NL; ++rb) {                    // (a padding block's T columns are zero: nothing to add)
+                    u32x4 af = af0;
+                    if (DROP) af = y_frag(rb);
+                    const u32x4 bf = t_frag(rb);
+                    // lanes of the accumulator run along the operand given SECOND: the contiguous index of C goes there
+                    acc[rb] = r_major ? mfma_32x32x16(bf, af, acc[rb]) : mfma_32x32x16(af, bf, acc[rb]);
+                }
+            } else if constexpr (TR > 32) {
+#pragma unroll
+                for (int jt = 0; jt < NT; ++jt) {                    // one fragment of the target's masked copy, TR / 32 MFMAs with it
+                    const u32x4 af = y_frag(jt);
+#pragma unroll
+                    for (int b = 0; b < TR / 32; ++b) {
+                        const int rb = jt * (TR / 32) + b;
+                        const u32x4 bf = t_frag(rb);
+                        acc[rb] = r_major ? mfma_32x32x16(bf, af, acc[rb]) : mfma_32x32x16(af, bf, acc[rb]);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int jt = 0; jt < NT; ++jt) {                    // the block's other targets' columns of T zeroed: exact zeros for them
+                    const int rb = jt * TR / 32;
+                    const u32x4 af = y_frag(jt);
+                    const u32x4 tf = t_frag(rb);
+                    const u32x4 bf = (lane & 31) / TR == jt % (32 / TR) ? tf : zero4;
+                    acc[rb] = r_major ? mfma_32x32x16(bf, af, acc[rb]) : mfma_32x32x16(af, bf, acc[rb]);
+                }
             }
         }
         if (DROP) __syncthreads();                   // every wave is done with the masked copies of step s
@@ -179,7 +213,8 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(WgradArgs g) {
 
 using namespace bra;
 
-static int wgrad_launch(WgradArgs& g, int m_chunk, bool drop, void* stream) {
+// tr / nt: adapter rank and targets of the launch (DROP); tr = 32: one target per live block
+static int wgrad_launch(WgradArgs& g, int m_chunk, bool drop, void* stream, int tr = 32, int nt = 0) {
     if (m_chunk <= 0) {
         // enough workgroups to fill the chip twice, at least 256 rows each
         const int ntile = (g.N + 127) / 128;
@@ -198,9 +233,21 @@ static int wgrad_launch(WgradArgs& g, int m_chunk, bool drop, void* stream) {
         else if (rm) BRA_LAUNCH((wgrad_tn_kernel<RB_, 0, RB_, 1>), grid, dim3(256), 0, st, g);    \
         else BRA_LAUNCH((wgrad_tn_kernel<RB_, 0, RB_, 0>), grid, dim3(256), 0, st, g);            \
     } while (0)
-    if (g.R == 32) BRA_WG(1, 1);
+#define BRA_WGR(RB_, NL_, TR_, NT_)                                                                      \
+    do {                                                                                                 \
+        if (rm) BRA_LAUNCH((wgrad_tn_kernel<RB_, 1, NL_, 1, TR_, NT_>), grid, dim3(256), 0, st, g);      \
+        else BRA_LAUNCH((wgrad_tn_kernel<RB_, 1, NL_, 0, TR_, NT_>), grid, dim3(256), 0, st, g);         \
+    } while (0)
+    if (drop && tr != 32) {
+        if (tr == 8) { if (nt == 1) BRA_WGR(2, 1, 8, 1); else if (nt == 2) BRA_WGR(2, 1, 8, 2); else BRA_WGR(2, 1, 8, 3); }
+        else if (tr == 16) { if (nt == 1) BRA_WGR(2, 1, 16, 1); else if (nt == 2) BRA_WGR(2, 1, 16, 2); else BRA_WGR(2, 2, 16, 3); }
+        else if (tr == 64) { if (g.R == 64) BRA_WGR(2, 2, 64, 1); else BRA_WGR(4, 4, 64, 2); }
+        else BRA_WGR(4, 4, 128, 1);
+    }
+    else if (g.R == 32) BRA_WG(1, 1);
     else if (g.R == 64) { if (drop && g.nb_live == 1) BRA_WG(2, 1); else BRA_WG(2, 2); }
     else { if (drop && g.nb_live == 3) BRA_WG(4, 3); else BRA_WG(4, 4); }
+#undef BRA_WGR
 #undef BRA_WG
     return BRA_LAUNCH_STATUS();
 }
@@ -208,9 +255,16 @@ static int wgrad_launch(WgradArgs& g, int m_chunk, bool drop, void* stream) {
 extern "C" int bra_wgrad_tn(const void* Y, long ldy, const void* T, long ldt, float* C, long c_sn, long c_sr, int M, int N,
                             int R, float alpha, int m_chunk, void* stream) {
     if (M == 0 || N == 0) return 0;
-    if (!Y || !T || !C || M < 0 || N < 0 || N % 8 || ldy % 8 || ldt % 8 || (R != 32 && R != 64 && R != 128)) return BRA_ERR_ARG;
-    WgradArgs g = {(const bf16_t*)Y, ldy, (const bf16_t*)T, ldt, C, c_sn, c_sr, M, N, R, 0, alpha, {}, R / 32};
-    return wgrad_launch(g, m_chunk, false, stream);
+    if (!Y || !T || !C || M < 0 || N < 0 || N % 8 || ldy % 8 || ldt % 8 || R <= 0 || (R != 32 && R % 64)) return BRA_ERR_ARG;
+    // a fused group wider than 128 rank columns (r = 64 x 3 targets: 192, r = 128: 256 / 384): one launch per slice of <= 128 columns
+    // of T and C (LDS tile and accumulators hold no more); R <= 128 is the single launch it always was
+    for (int c0 = 0; c0 < R; c0 += 128) {
+        const int Rs = R - c0 < 128 ? R - c0 : 128;
+        WgradArgs g = {(const bf16_t*)Y, ldy, (const bf16_t*)T + c0, ldt, C + (long)c0 * c_sr, c_sn, c_sr, M, N, Rs, 0, alpha, {}, Rs / 32};
+        const int rc = wgrad_launch(g, m_chunk, false, stream);
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 // the same with Y masked per rank block: dA of a LoRA branch whose input went through dropout (k_lora.hip)
@@ -226,4 +280,30 @@ extern "C" int bra_wgrad_tn_drop(const void* Y, long ldy, const void* T, long ld
     g.d.inv_keep = 1.f / (1.f - p);
     g.d.seed[0] = s0; g.d.seed[1] = s1; g.d.seed[2] = s2; g.d.seed[3] = s3;
     return wgrad_launch(g, m_chunk, true, stream);
+}
+
+// bra_wgrad_tn_drop for adapter rank r = 8 / 16 / 32 / 64 / 128 with `nt` <= 3 targets (target j = columns [j r, (j + 1) r) of T,
+// mask stream s_j; R = ceil(nt r / 64) 64); r = 32 is the entry point above.  Groups past 128 columns go slice by slice, each
+// with the seeds of its own targets
+extern "C" int bra_wgrad_tn_drop_r(const void* Y, long ldy, const void* T, long ldt, float* C, long c_sn, long c_sr, int M,
+                                   int N, int R, float alpha, int m_chunk, float p, unsigned s0, unsigned s1, unsigned s2,
+                                   int r, int nt, void* stream) {
+    const bool rank_ok = (r == 8 || r == 16 || r == 32 || r == 64 || r == 128) && nt >= 1 && nt <= 3 && R == (nt * r + 63) / 64 * 64;
+    if (r == 32 && rank_ok) return bra_wgrad_tn_drop(Y, ldy, T, ldt, C, c_sn, c_sr, M, N, R, alpha, m_chunk, p, s0, s1, s2, 0u, nt, stream);
+    if (M == 0 || N == 0) return 0;
+    if (!Y || !T || !C || M < 0 || N < 0 || N % 8 || ldy % 8 || ldt % 8 || !rank_ok) return BRA_ERR_ARG;
+    if (!(p >= 0.f && p < 1.f) || (long)M * N >= (1l << 32)) return BRA_ERR_ARG;
+    const unsigned seeds[3] = {s0, s1, s2};
+    for (int c0 = 0; c0 < R; c0 += 128) {
+        const int Rs = R - c0 < 128 ? R - c0 : 128;
+        const int j0 = r >= 64 ? c0 / r : 0, nts = r >= 64 ? Rs / r : nt;
+        WgradArgs g = {(const bf16_t*)Y, ldy, (const bf16_t*)T + c0, ldt, C + (long)c0 * c_sr, c_sn, c_sr, M, N, Rs, 0, alpha, {},
+                       (nts * r + 31) / 32};
+        g.d.thr16 = drop_threshold(p);
+        g.d.inv_keep = 1.f / (1.f - p);
+        for (int j = 0; j < 4; ++j) g.d.seed[j] = j < nts ? seeds[j0 + j] : 0u;
+        const int rc = wgrad_launch(g, m_chunk, true, stream, r, nts);
+        if (rc) return rc;
+    }
+    return 0;
 }

@@ -197,10 +197,10 @@ class QwenEngine:
 
     @staticmethod
     def _lora_fwd(x2d, W, G: Optional[LoraGroup], on: bool, res=None, out=None, drop=None):
-        """y = x W^T (+ (s dropout(x) A^T) B^T) (+res); returns (y, t).  drop = (p, seeds per target) in training mode"""
+        """y = x W^T (+ (s dropout(x) A^T) B^T) (+res); returns (y, t).  drop = (p, seeds per target, rank) in training mode"""
         if G is not None and on:
             if drop is not None:
-                t = ops.lora_down_drop(x2d, G.A, G.scaling, drop[0], drop[1])
+                t = ops.lora_down_drop(x2d, G.A, G.scaling, drop[0], drop[1], drop[2])
             else:
                 t = QwenEngine._down(x2d, G.A, G.scaling, len(G.n_sizes) * G.r)
             return ops.gemm_nt(x2d, W, a2=t, b2=G.B, res=res, out=out), t
@@ -212,13 +212,14 @@ class QwenEngine:
         if G is not None and on:
             dts = QwenEngine._down(dy, G.BT, G.scaling, len(G.n_sizes) * G.r)   # [T, r_pad] = s * dy B
             if drop is not None:
-                dxl = ops.lora_up_drop(dts, G.AT, drop[0], drop[1])      # the branch's input gradient, masked per target
+                dxl = ops.lora_up_drop(dts, G.AT, drop[0], drop[1], drop[2])   # the branch's input gradient, masked per target
                 dx = ops.gemm_nt(dy, WT, res=dxl)
             else:
                 dx = ops.gemm_nt(dy, WT, a2=dts, b2=G.AT)
             # weight gradients straight from the row-major activations (k_wgrad.hip): no transposed copies in HBM
             ops.wgrad_tn(dy, t, G.B_grad)                                # dB [N, r] += dy^T t      (t already holds s)
-            ops.wgrad_tn(x2d, dts, G.A_grad, transposed_out=True, drop=drop)   # dA [r, K] += (s dy B)^T dropout(x)
+            ops.wgrad_tn(x2d, dts, G.A_grad, transposed_out=True, drop=drop[:2] if drop is not None else None,
+                         rank=drop[2] if drop is not None else 32)       # dA [r, K] += (s dy B)^T dropout(x)
             return dx
         return ops.gemm_nt(dy, WT)
 
@@ -226,9 +227,10 @@ class QwenEngine:
         G = self.layers[li].lora[group]
         if G is None or not m.lora_on or m.drop_p <= 0.0:
             return None
-        if G.r != 32:
-            raise NotImplementedError("LoRA dropout needs r = 32 (one mask stream per 32-column rank block)")
-        return (m.drop_p, lora_drop_seeds(m.drop_seed, li, group, len(G.n_sizes)))
+        if G.r not in ops.LORA_DROP_RANKS:
+            raise NotImplementedError(f"LoRA dropout needs an adapter rank in {list(ops.LORA_DROP_RANKS)} (one mask stream per target "
+                                      f"module, built for these ranks), not r = {G.r}")
+        return (m.drop_p, lora_drop_seeds(m.drop_seed, li, group, len(G.n_sizes)), G.r)
 
     # ------------------------------------------------------------------ fp8 x fp8 projections (opt-in; BASELINE config 5)
     def use_fp8(self, W8):
@@ -329,7 +331,7 @@ class QwenEngine:
             # values in one launch, no [T, 2 F] intermediate); None where the fused kernel does not apply
             G3, d3 = L.lora["gu"], self._drop(m, li, "gu")
             if G3 is not None and m.lora_on:
-                t3 = ops.lora_down_drop(hn, G3.A, G3.scaling, d3[0], d3[1]) if d3 is not None else self._down(hn, G3.A, G3.scaling, len(G3.n_sizes) * G3.r)
+                t3 = ops.lora_down_drop(hn, G3.A, G3.scaling, d3[0], d3[1], d3[2]) if d3 is not None else self._down(hn, G3.A, G3.scaling, len(G3.n_sizes) * G3.r)
                 act = ops.gemm_swiglu(hn, L.Wgu, a2=t3, b2=G3.B)
             else:
                 act = ops.gemm_swiglu(hn, L.Wgu)

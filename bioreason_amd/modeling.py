@@ -311,8 +311,9 @@ class Qwen3ForCausalLM(nn.Module):
         init_lora_weights="gaussian")) on the text model (train_dna_qwen.py:155-167)."""
         if dropout < 0.0 or dropout >= 1.0:
             raise ValueError("lora_dropout must be in [0, 1)")
-        if dropout > 0.0 and r != 32:
-            raise NotImplementedError("lora_dropout > 0 needs r = 32 in the HIP path (one mask stream per 32-column rank block)")
+        if dropout > 0.0 and r not in ops.LORA_DROP_RANKS:
+            raise NotImplementedError(f"lora_dropout > 0 needs r in {list(ops.LORA_DROP_RANKS)} in the HIP path (the masked LoRA kernels "
+                                      f"are built for these ranks), not r = {r}; any rank works with lora_dropout = 0")
         self.lora_dropout_p = float(dropout)      # active in training mode with adapters enabled (nn.Dropout of PEFT's LoraLayer)
         dev = self.device
         self.arena = arena or self.arena or TrainableArena(dev)

@@ -142,13 +142,18 @@ def gemm_nt_splitk(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, alpha: f
 
 
 def wgrad_tn(y: torch.Tensor, t: torch.Tensor, out: torch.Tensor, transposed_out: bool = False, alpha: float = 1.0,
-             m_chunk: int = 0, drop=None) -> torch.Tensor:
-    """out += alpha * y^T t from row-major y [M, N], t [M, R]: out [N, R], or [R, N] with transposed_out.
-    drop = (p, seeds): y is used as dropout_rb(y), one mask stream per 32 columns of t."""
+             m_chunk: int = 0, drop=None, rank: int = 32) -> torch.Tensor:
+    """out += alpha * y^T t from row-major y [M, N], t [M, R]: out [N, R], or [R, N] with transposed_out.  R = 32 or a multiple of 64.
+    drop = (p, seeds): y is used as dropout_j(y), one mask stream per target = per `rank` columns of t (seeds[j] for columns
+    [j rank, (j + 1) rank); rank in LORA_DROP_RANKS, R = the group's padded width)."""
     M, N = y.shape
     R = t.shape[1]
     assert t.shape[0] == M and out.dtype == torch.float32 and out.shape == ((R, N) if transposed_out else (N, R))
     c_sn, c_sr = (1, _ld(out)) if transposed_out else (_ld(out), 1)
+    if drop is not None and rank != 32:
+        get_lib().call("bra_wgrad_tn_drop_r", y, _ld(y), t, _ld(t), out, c_sn, c_sr, M, N, R, alpha, m_chunk, drop[0],
+                       *_seeds3(drop[1], rank), rank, len(drop[1]), current_stream(y))
+        return out
     if drop is not None:
         get_lib().call("bra_wgrad_tn_drop", y, _ld(y), t, _ld(t), out, c_sn, c_sr, M, N, R, alpha, m_chunk, drop[0],
                        *_seeds4(drop[1]), min(len(drop[1]), 4), current_stream(y))
@@ -162,6 +167,19 @@ def _seeds4(seeds):
     return s[:4]
 
 
+LORA_DROP_RANKS = (8, 16, 32, 64, 128)          # adapter ranks the masked LoRA kernels are built for (k_lora.hip, k_wgrad.hip)
+
+
+def _seeds3(seeds, rank):
+    """(s0, s1, s2) of the bra_*_r entry points: one seed per target module, at most three targets in a fused group"""
+    if rank not in LORA_DROP_RANKS:
+        raise NotImplementedError(f"LoRA dropout is built for adapter ranks {list(LORA_DROP_RANKS)}, not r = {rank}")
+    if not 1 <= len(seeds) <= 3:
+        raise ValueError(f"a fused LoRA group has 1 to 3 targets, got {len(seeds)} seeds")
+    s = [int(x) & 0xFFFFFFFF for x in seeds] + [0, 0]
+    return s[:3]
+
+
 def dropout_mask(M: int, K: int, p: float, seed: int, device) -> torch.Tensor:
     """keep mask (uint8 [M, K]) of one dropout stream — the mask the LoRA kernels regenerate on the fly"""
     out = torch.empty((M, K), dtype=torch.uint8, device=device)
@@ -172,13 +190,23 @@ def dropout_mask(M: int, K: int, p: float, seed: int, device) -> torch.Tensor:
 LORA_DOWN_SPLITK = os.environ.get("BRA_LORA_SPLITK", "1") != "0"
 
 
-def lora_down_drop(x: torch.Tensor, A: torch.Tensor, alpha: float, p: float, seeds) -> torch.Tensor:
-    """t [M, R] = alpha * dropout_j(x) A^T with one mask stream per 32 rows of A (PEFT: per target module)"""
+def lora_down_drop(x: torch.Tensor, A: torch.Tensor, alpha: float, p: float, seeds, rank: int = 32) -> torch.Tensor:
+    """t [M, R] = alpha * dropout_j(x) A^T with one mask stream per target module (PEFT): target j = rows [j rank, (j + 1) rank) of
+    A, seeds[j].  rank in LORA_DROP_RANKS; A is the group's padded image, R = ceil(targets * rank / 64) * 64 (rank 32: 32 / 64 / 128)"""
     M, K = x.shape
     R = A.shape[0]
     t = torch.empty((M, R), dtype=BF16, device=x.device)
     lib = get_lib()
     ks = int(lib._dll.bra_lora_down_splitk_plan(int(M), int(K))) if LORA_DOWN_SPLITK else 1
+    if rank != 32:
+        s3 = _seeds3(seeds, rank)
+        if ks > 1:
+            part = torch.empty((ks, M, R), dtype=torch.float32, device=x.device)
+            lib.call("bra_lora_down_drop_splitk_r", x, _ld(x), A, _ld(A), t, _ld(t), M, K, R, alpha, p, *s3, rank, len(seeds), part, ks,
+                     current_stream(x))
+        else:
+            lib.call("bra_lora_down_drop_r", x, _ld(x), A, _ld(A), t, _ld(t), M, K, R, alpha, p, *s3, rank, len(seeds), current_stream(x))
+        return t
     if ks > 1:
         part = torch.empty((ks, M, R), dtype=torch.float32, device=x.device)
         lib.call("bra_lora_down_drop_splitk", x, _ld(x), A, _ld(A), t, _ld(t), M, K, R, alpha, p, *_seeds4(seeds), min(len(seeds), 4),
@@ -189,11 +217,16 @@ def lora_down_drop(x: torch.Tensor, A: torch.Tensor, alpha: float, p: float, see
     return t
 
 
-def lora_up_drop(dts: torch.Tensor, AT: torch.Tensor, p: float, seeds) -> torch.Tensor:
-    """[M, K] = sum_j dropout_j'(dts[:, block j] A[block j, :]): input gradient of the LoRA branch (AT = A^T [K, R])"""
+def lora_up_drop(dts: torch.Tensor, AT: torch.Tensor, p: float, seeds, rank: int = 32) -> torch.Tensor:
+    """[M, K] = sum_j dropout_j'(dts[:, target j] A[target j, :]): input gradient of the LoRA branch (AT = A^T [K, R]); target j =
+    rank columns [j rank, (j + 1) rank), seeds[j]"""
     M, R = dts.shape
     K = AT.shape[0]
     out = torch.empty((M, K), dtype=BF16, device=dts.device)
+    if rank != 32:
+        get_lib().call("bra_lora_up_drop_r", dts, _ld(dts), AT, _ld(AT), out, _ld(out), M, K, R, p, *_seeds3(seeds, rank), rank, len(seeds),
+                       current_stream(dts))
+        return out
     get_lib().call("bra_lora_up_drop", dts, _ld(dts), AT, _ld(AT), out, _ld(out), M, K, R, p, *_seeds4(seeds), min(len(seeds), 4),
                    current_stream(dts))
     return out

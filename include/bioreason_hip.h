@@ -52,16 +52,17 @@ int bra_gemm_bf16_nt_splitk(const void* A, long lda, const void* B, long ldb, vo
                             float alpha, int split_k, void* stream);
 
 /* Low-rank weight gradient from ROW-MAJOR operands (k_wgrad.hip): C[n, r] += alpha * sum_m Y[m, n] T[m, r], Y [M, N]
- * bf16, T [M, R] bf16 with R in {32, 64, 128}; C fp32 addressed by element strides (c_sn, c_sr), so the same call
+ * bf16, T [M, R] bf16 with R = 32 or any multiple of 64 (a fused LoRA group of any rank: past 128 columns the call walks T and
+ * C in slices of <= 128 columns, one launch each); C fp32 addressed by element strides (c_sn, c_sr), so the same call
  * writes dB [N_out, r] (Y = dy, T = s x A^T) and dA [r, K] transposed (Y = x, T = s dy B) — autograd of PEFT's
  * lora_B / lora_A.  m_chunk = rows per workgroup (0: chosen to fill the chip); combined by fp32 atomics. */
 int bra_wgrad_tn(const void* Y, long ldy, const void* T, long ldt, float* C, long c_sn, long c_sr, int M, int N, int R,
                  float alpha, int m_chunk, void* stream);
 
 /* LoRA branch under training-mode dropout (k_lora.hip; PEFT: y += (alpha/r) B(A(dropout(x))), lora_dropout 0.05,
- * reason.py:266,376-388).  Every 32-column rank block (= target module of a fused projection) has its own mask stream
- * s0..s3, as PEFT gives every target its own nn.Dropout; keep(seed, m, k) is a hash of the element index m*K + k, so no
- * mask is stored.  R in {32, 64, 128}; M*K < 2^32.
+ * reason.py:266,376-388).  Every target module of a fused projection has its own mask stream, as PEFT gives every target its
+ * own nn.Dropout; keep(seed, m, k) is a hash of the element index m*K + k, so no mask is stored.  M*K < 2^32.
+ * Adapter rank 32 (the entry points without _r): a target is one 32-column rank block, streams s0..s3, R in {32, 64, 128}.
  *   bra_lora_down_drop: t[M,R] = alpha * (drop_j(x) A^T)              x [M,K], A [R,K]
  *   bra_lora_up_drop:   out[M,K] = sum_j drop_j'( dts[:, j] A[j, :] )  dts [M,R], AT [K,R]   (input gradient of the branch)
  *   bra_wgrad_tn_drop:  bra_wgrad_tn with Y = drop_rb(Y)               (dA of the branch)
@@ -83,6 +84,20 @@ int bra_lora_up_drop(const void* dts, long ldd, const void* AT, long ldat, void*
 int bra_wgrad_tn_drop(const void* Y, long ldy, const void* T, long ldt, float* C, long c_sn, long c_sr, int M, int N, int R,
                       float alpha, int m_chunk, float p, unsigned s0, unsigned s1, unsigned s2, unsigned s3, int nb_live,
                       void* stream);
+/* The same for adapter rank r in {8, 16, 32, 64, 128} (`lora_r` / `--lora_rank` of the reference scripts) and nt <= 3 targets:
+ * target j owns rank columns [j r, (j + 1) r) and mask stream s_j; R = ceil(nt r / 64) * 64 (the fused group's padded width; the
+ * columns past nt r are padding: zeros in t, never masked).  r >= 64: a target spans r / 32 blocks and its masked operand is built
+ * once for all of them; r < 32: the 32 / r targets of a block each get their own masked operand.  Groups wider than 128 columns
+ * (r = 64 x 3, r = 128 x 2 / 3) are walked in slices of <= 128 columns by down and wgrad.  r = 32 forwards to the entry points
+ * above.  `part` of the split-K form: [ksplit, M, R] floats. */
+int bra_lora_down_drop_r(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R, float alpha,
+                         float p, unsigned s0, unsigned s1, unsigned s2, int r, int nt, void* stream);
+int bra_lora_down_drop_splitk_r(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R, float alpha,
+                                float p, unsigned s0, unsigned s1, unsigned s2, int r, int nt, float* part, int ksplit, void* stream);
+int bra_lora_up_drop_r(const void* dts, long ldd, const void* AT, long ldat, void* out, long ldo, int M, int K, int R, float p,
+                       unsigned s0, unsigned s1, unsigned s2, int r, int nt, void* stream);
+int bra_wgrad_tn_drop_r(const void* Y, long ldy, const void* T, long ldt, float* C, long c_sn, long c_sr, int M, int N, int R,
+                        float alpha, int m_chunk, float p, unsigned s0, unsigned s1, unsigned s2, int r, int nt, void* stream);
 int bra_dropout_mask(void* out, int M, int K, float p, unsigned seed, void* stream);
 
 /* Fused lm_head + log-softmax statistics WITHOUT materialising logits
