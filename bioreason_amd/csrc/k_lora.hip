@@ -9,18 +9,18 @@
 //   wgrad_tn (DROP)  dA[r, k] += sum_m dts[m,r] keep_j(m,k)/(1-p) x[m,k]               (k_wgrad.hip)
 // with j = column / r.  torch's dropout scales in fp32 and rounds once to bf16; so does drop_apply8.
 // The MFMA tile is 32 rank columns wide, so the adapter rank r (template parameter TR) decides how targets meet tiles:
-//   r = 32      one target = one 32-column block (the bench's shape; the entry points without _r, bit for bit as before)
+//   r = 32      one target = one 32-column block (the bench's shape)
 //   r = 64, 128 a target spans r / 32 blocks: its masked operand is built ONCE and feeds all of its MFMAs (the hash is the
 //               bound of these kernels, bra_dropout.h — never one hash per block)
 //   r = 8, 16   32 / r targets share a block: each gets its own masked operand and its own MFMA, with the other targets'
 //               rank rows (down, wgrad) or k elements (up) of the second operand zeroed in registers — the products they
 //               would add are exact zeros, so the block keeps ONE accumulator
-// The bra_*_r entry points carry (r, targets) and expect the LoraGroup layout R = ceil(targets r / 64) 64; groups wider than
-// 128 columns (r = 64 x 3, r = 128 x 2 / 3) are walked in slices of <= 128 columns by the launchers (down, wgrad: LDS and
-// accumulators do not fit more), each slice with the seeds of its own targets.
+// Every entry point carries (r, targets) and expects the LoraGroup layout R = ceil(targets r / 64) 64 (r = 32 also R = 32 and up to
+// four targets: include/bioreason_hip.h); groups wider than 128 columns (r = 64 x 3, r = 128 x 2 / 3) are walked in slices of <= 128
+// columns by down and wgrad, each slice with the seeds of its own targets.  Contract, slices and instantiation table: bra_lora_plan.h.
 #include "bra_device.h"
 #include "bra_api_internal.h"
-#include "bra_dropout.h"
+#include "bra_lora_plan.h"
 
 namespace bra {
 
@@ -31,7 +31,7 @@ struct LoraDownArgs {
     int M, K, R;
     float alpha;
     DropCfg d;
-    int nb_live;                    // rank blocks that belong to a target module; the padding blocks behind them produce zeros
+    int nb_live;                    // no longer read (NL is compile-time): kept so that the argument layout stays as it is
     int steps_per;                  // K steps (of 128) per workgroup along gridDim.y (split-K form), nstep when gridDim.y == 1
     float* part;                    // split-K form: fp32 partial tiles [gridDim.y][M][R] (unscaled) instead of t
 };
@@ -197,7 +197,7 @@ struct LoraUpArgs {
     int M, K, R;
     int k_chunk;                    // columns per workgroup (multiple of 32)
     DropCfg d;
-    int nb_live;                    // rank blocks that belong to a target module (padding blocks contribute nothing)
+    int nb_live;                    // no longer read (NL is compile-time): kept so that the argument layout stays as it is
 };
 
 // wave = 32 rows of dts, walks 32-column tiles of the output; rank-TR product per target, masked, summed over targets.
@@ -304,22 +304,6 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(uint8_t* out, long n,
 
 using namespace bra;
 
-static DropCfg make_cfg(float p, unsigned s0, unsigned s1, unsigned s2, unsigned s3) {
-    DropCfg d;
-    d.thr16 = drop_threshold(p);
-    d.inv_keep = 1.f / (1.f - p);
-    d.seed[0] = s0; d.seed[1] = s1; d.seed[2] = s2; d.seed[3] = s3;
-    return d;
-}
-
-static int lora_down_launch(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R, float alpha, float p,
-                            unsigned s0, unsigned s1, unsigned s2, unsigned s3, int nb_live, float* part, int ksplit, void* stream);
-
-extern "C" int bra_lora_down_drop(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R,
-                                  float alpha, float p, unsigned s0, unsigned s1, unsigned s2, unsigned s3, int nb_live, void* stream) {
-    return lora_down_launch(x, ldx, A, lda, t, ldt, M, K, R, alpha, p, s0, s1, s2, s3, nb_live, nullptr, 1, stream);
-}
-
 extern "C" int bra_lora_down_splitk_plan(int M, int K) {
     // workgroups per row block so that the grid reaches ~2 per CU while every workgroup keeps >= 3 K steps (its prologue is one step)
     const int gx = (M + 31) / 32, nstep = (K + 127) / 128;
@@ -335,143 +319,64 @@ extern "C" int bra_lora_down_splitk_plan(int M, int K) {
     return (nstep + per - 1) / per;
 }
 
-extern "C" int bra_lora_down_drop_splitk(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R,
-                                         float alpha, float p, unsigned s0, unsigned s1, unsigned s2, unsigned s3, int nb_live,
-                                         float* part, int ksplit, void* stream) {
-    if (ksplit <= 1) return lora_down_launch(x, ldx, A, lda, t, ldt, M, K, R, alpha, p, s0, s1, s2, s3, nb_live, nullptr, 1, stream);
-    if (!part || ksplit > (K + 127) / 128 || ldt % 4) return BRA_ERR_ARG;
-    return lora_down_launch(x, ldx, A, lda, t, ldt, M, K, R, alpha, p, s0, s1, s2, s3, nb_live, part, ksplit, stream);
-}
-
-static int lora_down_launch(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R, float alpha, float p,
-                            unsigned s0, unsigned s1, unsigned s2, unsigned s3, int nb_live, float* part, int ksplit, void* stream) {
+// ksplit <= 1: the plain form; else `part` holds [ksplit, M, Rs] floats per slice, the tiles of the slice at column c0 at part + ksplit M c0
+extern "C" int bra_lora_down_drop(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R,
+                                  float alpha, float p, unsigned s0, unsigned s1, unsigned s2, unsigned s3, int r, int nt,
+                                  float* part, int ksplit, void* stream) {
     if (M == 0) return 0;
-    if (!x || !A || !t || M < 0 || K <= 0 || K % 8 || ldx % 8 || lda % 8 || (R != 32 && R != 64 && R != 128)) return BRA_ERR_ARG;
-    if (!(p >= 0.f && p < 1.f) || (long)M * K >= (1l << 32)) return BRA_ERR_ARG;
-    if (nb_live <= 0 || nb_live > R / 32) nb_live = R / 32;
+    if (!x || !A || !t || M < 0 || K <= 0 || K % 8 || ldx % 8 || lda % 8 || !lora_drop_ok(p, M, K, r, nt, R)) return BRA_ERR_ARG;
+    if (ksplit <= 1) part = nullptr;
+    else if (!part || ksplit > (K + 127) / 128 || ldt % 4) return BRA_ERR_ARG;
+    const unsigned seeds[4] = {s0, s1, s2, s3};
     const int nstep = (K + 127) / 128;
     const int per = part ? (nstep + ksplit - 1) / ksplit : nstep;
     const int ny = part ? (nstep + per - 1) / per : 1;                 // no empty workgroup
-    LoraDownArgs g = {(const bf16_t*)x, ldx, (const bf16_t*)A, lda, (bf16_t*)t, ldt, M, K, R, alpha, make_cfg(p, s0, s1, s2, s3), nb_live,
-                      per, part};
     const dim3 grid((M + 31) / 32, ny);
     bra_stream_t st = (bra_stream_t)stream;
-#define BRA_LD(RB_, NL_) BRA_LAUNCH((lora_down_drop_kernel<RB_, NL_>), grid, dim3(256), 0, st, g)
-    if (R == 32) BRA_LD(1, 1);
-    else if (R == 64) { if (nb_live == 1) BRA_LD(2, 1); else BRA_LD(2, 2); }
-    else { if (nb_live == 3) BRA_LD(4, 3); else if (nb_live == 4) BRA_LD(4, 4); else { g.nb_live = 4; BRA_LD(4, 4); } }
+    return lora_for_slices(r, nt, R, [&](const LoraSlice& s) {
+        float* const ps = part ? part + (long)ksplit * M * s.c0 : nullptr;
+        bf16_t* const ts = (bf16_t*)t + s.c0;
+        LoraDownArgs g = {(const bf16_t*)x, ldx, (const bf16_t*)A + (long)s.c0 * lda, lda, ts, ldt, M, K, s.Rs, alpha,
+                          make_cfg(p, seeds + s.j0, s.nts), 0, per, ps};
+#define BRA_LD(C_, RB_, NL_, TR_, NT_) if (C_) BRA_LAUNCH((lora_down_drop_kernel<RB_, NL_, TR_, NT_>), grid, dim3(256), 0, st, g); else
+        BRA_LORA_ROWS(BRA_LD) return BRA_ERR_ARG;
 #undef BRA_LD
-    if (part) {
-        const long MR = (long)M * R;
-        BRA_LAUNCH(lora_partial_reduce_kernel, dim3((unsigned)((MR / 4 + 255) / 256)), dim3(256), 0, st, (const float*)part, ny, MR, R, alpha,
-                   (bf16_t*)t, ldt);
-    }
-    return BRA_LAUNCH_STATUS();
-}
-
-// (r, targets) of the _r entry points: the ranks with a masked kernel, in the LoraGroup layout
-static bool lora_rank_ok(int r, int nt, int R) {
-    return (r == 8 || r == 16 || r == 32 || r == 64 || r == 128) && nt >= 1 && nt <= 3 && R == (nt * r + 63) / 64 * 64;
-}
-
-static int lora_down_launch_r(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R, float alpha, float p,
-                              const unsigned* seeds, int r, int nt, float* part, int ksplit, void* stream) {
-    if (M == 0) return 0;
-    if (!x || !A || !t || M < 0 || K <= 0 || K % 8 || ldx % 8 || lda % 8 || !lora_rank_ok(r, nt, R)) return BRA_ERR_ARG;
-    if (!(p >= 0.f && p < 1.f) || (long)M * K >= (1l << 32)) return BRA_ERR_ARG;
-    const int nstep = (K + 127) / 128;
-    const int per = part ? (nstep + ksplit - 1) / ksplit : nstep;
-    const int ny = part ? (nstep + per - 1) / per : 1;
-    const dim3 grid((M + 31) / 32, ny);
-    bra_stream_t st = (bra_stream_t)stream;
-    // slices of <= 128 rank columns (r >= 64: whole targets, R = targets * r; r < 32: R = 64, one slice)
-    for (int c0 = 0; c0 < R; c0 += 128) {
-        const int Rs = R - c0 < 128 ? R - c0 : 128;
-        const int j0 = r >= 64 ? c0 / r : 0, nts = r >= 64 ? Rs / r : nt;
-        float* const ps = part ? part + (long)ksplit * M * c0 : nullptr;
-        bf16_t* const ts = (bf16_t*)t + c0;
-        LoraDownArgs g = {(const bf16_t*)x, ldx, (const bf16_t*)A + (long)c0 * lda, lda, ts, ldt, M, K, Rs, alpha,
-                          make_cfg(p, seeds[j0], nts > 1 ? seeds[j0 + 1] : 0u, nts > 2 ? seeds[j0 + 2] : 0u, 0u), (nts * r + 31) / 32, per, ps};
-#define BRA_LDR(RB_, NL_, TR_, NT_) BRA_LAUNCH((lora_down_drop_kernel<RB_, NL_, TR_, NT_>), grid, dim3(256), 0, st, g)
-        if (r == 8) { if (nts == 1) BRA_LDR(2, 1, 8, 1); else if (nts == 2) BRA_LDR(2, 1, 8, 2); else BRA_LDR(2, 1, 8, 3); }
-        else if (r == 16) { if (nts == 1) BRA_LDR(2, 1, 16, 1); else if (nts == 2) BRA_LDR(2, 1, 16, 2); else BRA_LDR(2, 2, 16, 3); }
-        else if (r == 64) { if (Rs == 64) BRA_LDR(2, 2, 64, 1); else BRA_LDR(4, 4, 64, 2); }
-        else BRA_LDR(4, 4, 128, 1);
-#undef BRA_LDR
         if (part) {
-            const long MR = (long)M * Rs;
-            BRA_LAUNCH(lora_partial_reduce_kernel, dim3((unsigned)((MR / 4 + 255) / 256)), dim3(256), 0, st, (const float*)ps, ny, MR, Rs, alpha,
-                       ts, ldt);
+            const long MR = (long)M * s.Rs;
+            BRA_LAUNCH(lora_partial_reduce_kernel, dim3((unsigned)((MR / 4 + 255) / 256)), dim3(256), 0, st, (const float*)ps, ny, MR, s.Rs,
+                       alpha, ts, ldt);
         }
-    }
-    return BRA_LAUNCH_STATUS();
-}
-
-// the same three kernels for adapter rank r = 8 / 16 / 32 / 64 / 128 with `nt` <= 3 targets: target j = rank columns
-// [j r, (j + 1) r), mask stream s_j; R = ceil(nt r / 64) 64.  r = 32 is the form above, through the same instantiations
-extern "C" int bra_lora_down_drop_r(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R,
-                                    float alpha, float p, unsigned s0, unsigned s1, unsigned s2, int r, int nt, void* stream) {
-    if (r == 32 && lora_rank_ok(r, nt, R)) return bra_lora_down_drop(x, ldx, A, lda, t, ldt, M, K, R, alpha, p, s0, s1, s2, 0u, nt, stream);
-    const unsigned seeds[3] = {s0, s1, s2};
-    return lora_down_launch_r(x, ldx, A, lda, t, ldt, M, K, R, alpha, p, seeds, r, nt, nullptr, 1, stream);
-}
-
-// part: [ksplit, M, R] floats
-extern "C" int bra_lora_down_drop_splitk_r(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R,
-                                           float alpha, float p, unsigned s0, unsigned s1, unsigned s2, int r, int nt, float* part,
-                                           int ksplit, void* stream) {
-    if (r == 32 && lora_rank_ok(r, nt, R))
-        return bra_lora_down_drop_splitk(x, ldx, A, lda, t, ldt, M, K, R, alpha, p, s0, s1, s2, 0u, nt, part, ksplit, stream);
-    const unsigned seeds[3] = {s0, s1, s2};
-    if (ksplit <= 1) return lora_down_launch_r(x, ldx, A, lda, t, ldt, M, K, R, alpha, p, seeds, r, nt, nullptr, 1, stream);
-    if (!part || ksplit > (K + 127) / 128 || ldt % 4) return BRA_ERR_ARG;
-    return lora_down_launch_r(x, ldx, A, lda, t, ldt, M, K, R, alpha, p, seeds, r, nt, part, ksplit, stream);
+        return BRA_LAUNCH_STATUS();
+    });
 }
 
 extern "C" int bra_lora_up_drop(const void* dts, long ldd, const void* AT, long ldat, void* out, long ldo, int M, int K, int R,
-                                float p, unsigned s0, unsigned s1, unsigned s2, unsigned s3, int nb_live, void* stream) {
+                                float p, unsigned s0, unsigned s1, unsigned s2, unsigned s3, int r, int nt, void* stream) {
     if (M == 0) return 0;
-    if (!dts || !AT || !out || M < 0 || K <= 0 || ldd % 8 || ldat % 8 || (R != 32 && R != 64 && R != 128)) return BRA_ERR_ARG;
-    if (!(p >= 0.f && p < 1.f) || (long)M * K >= (1l << 32)) return BRA_ERR_ARG;
+    if (!dts || !AT || !out || M < 0 || K <= 0 || ldd % 8 || ldat % 8 || !lora_drop_ok(p, M, K, r, nt, R)) return BRA_ERR_ARG;
     const int mblk = (M + 127) / 128;
     int splits = (1024 + mblk - 1) / mblk;                       // enough workgroups to fill the chip
     int k_chunk = ((K + splits - 1) / splits + 31) / 32 * 32;
     k_chunk = k_chunk < 128 ? 128 : k_chunk;
-    if (nb_live <= 0 || nb_live > R / 32) nb_live = R / 32;
-    LoraUpArgs g = {(const bf16_t*)dts, ldd, (const bf16_t*)AT, ldat, (bf16_t*)out, ldo, M, K, R, k_chunk, make_cfg(p, s0, s1, s2, s3), nb_live};
+    const unsigned seeds[4] = {s0, s1, s2, s3};
+    LoraUpArgs g = {(const bf16_t*)dts, ldd, (const bf16_t*)AT, ldat, (bf16_t*)out, ldo, M, K, R, k_chunk, make_cfg(p, seeds, nt), 0};
     const dim3 grid(mblk, (K + k_chunk - 1) / k_chunk);
     bra_stream_t st = (bra_stream_t)stream;
-#define BRA_LU(RB_, NL_) BRA_LAUNCH((lora_up_drop_kernel<RB_, NL_>), grid, dim3(256), 0, st, g)
-    if (R == 32) BRA_LU(1, 1);
-    else if (R == 64) { if (nb_live == 1) BRA_LU(2, 1); else BRA_LU(2, 2); }
-    else { if (nb_live == 3) BRA_LU(4, 3); else BRA_LU(4, 4); }        // (padding blocks hold zeros: treating them as live is exact, only slower)
-#undef BRA_LU
-    return BRA_LAUNCH_STATUS();
-}
-
-extern "C" int bra_lora_up_drop_r(const void* dts, long ldd, const void* AT, long ldat, void* out, long ldo, int M, int K, int R,
-                                  float p, unsigned s0, unsigned s1, unsigned s2, int r, int nt, void* stream) {
-    if (r == 32 && lora_rank_ok(r, nt, R)) return bra_lora_up_drop(dts, ldd, AT, ldat, out, ldo, M, K, R, p, s0, s1, s2, 0u, nt, stream);
-    if (M == 0) return 0;
-    if (!dts || !AT || !out || M < 0 || K <= 0 || ldd % 8 || ldat % 8 || !lora_rank_ok(r, nt, R)) return BRA_ERR_ARG;
-    if (!(p >= 0.f && p < 1.f) || (long)M * K >= (1l << 32)) return BRA_ERR_ARG;
-    const int mblk = (M + 127) / 128;
-    int splits = (1024 + mblk - 1) / mblk;
-    int k_chunk = ((K + splits - 1) / splits + 31) / 32 * 32;
-    k_chunk = k_chunk < 128 ? 128 : k_chunk;
-    LoraUpArgs g = {(const bf16_t*)dts, ldd, (const bf16_t*)AT, ldat, (bf16_t*)out, ldo, M, K, R, k_chunk, make_cfg(p, s0, s1, s2, 0u),
-                    (nt * r + 31) / 32};
-    const dim3 grid(mblk, (K + k_chunk - 1) / k_chunk);
-    bra_stream_t st = (bra_stream_t)stream;
-    // the whole group in one launch, whatever its width: only dts / A fragments grow with it (8 registers per 32 columns each)
-#define BRA_LUR(TR_, NT_) BRA_LAUNCH((lora_up_drop_kernel<(NT_ * TR_ + 63) / 64 * 2, (NT_ * TR_ + 31) / 32, TR_, NT_>), grid, dim3(256), 0, st, g)
+    // the whole group in one launch, whatever its width (bra_lora_plan.h): RB / NL follow from the columns the targets cover
+#define BRA_LU(RB_, NL_, TR_, NT_) BRA_LAUNCH((lora_up_drop_kernel<RB_, NL_, TR_, NT_>), grid, dim3(256), 0, st, g)
+#define BRA_LUR(TR_, NT_) BRA_LU((NT_ * TR_ + 63) / 64 * 2, (NT_ * TR_ + 31) / 32, TR_, NT_)
 #define BRA_LUR3(TR_) do { if (nt == 1) BRA_LUR(TR_, 1); else if (nt == 2) BRA_LUR(TR_, 2); else BRA_LUR(TR_, 3); } while (0)
-    if (r == 8) BRA_LUR3(8);
+    if (r == 32 && R == 32) BRA_LU(1, 1, 32, 1);
+    else if (r == 32 && R == 64) { if (nt == 1) BRA_LU(2, 1, 32, 1); else BRA_LU(2, 2, 32, 2); }
+    else if (r == 32 && nt == 3) BRA_LU(4, 3, 32, 3);
+    else if (r == 32) BRA_LU(4, 4, 32, 4);     // nt = 4; nt = 1 / 2 at R = 128: padding blocks hold zeros, treating them as live is exact
+    else if (r == 8) BRA_LUR3(8);
     else if (r == 16) BRA_LUR3(16);
     else if (r == 64) BRA_LUR3(64);
     else BRA_LUR3(128);
 #undef BRA_LUR3
 #undef BRA_LUR
+#undef BRA_LU
     return BRA_LAUNCH_STATUS();
 }
 

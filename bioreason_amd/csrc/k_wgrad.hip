@@ -10,7 +10,7 @@
 // streaming Y once from HBM (≈16 FLOP per byte).
 #include "bra_device.h"
 #include "bra_api_internal.h"
-#include "bra_dropout.h"
+#include "bra_lora_plan.h"
 
 namespace bra {
 
@@ -22,7 +22,7 @@ struct WgradArgs {
     int m_chunk;                    // rows of m per workgroup (multiple of 32)
     float alpha;
     DropCfg d;                      // DROP: Y is used as keep_j(m, n) / (1 - p) * Y[m, n], one mask stream per target j (TR columns of T)
-    int nb_live;                    // DROP: rank blocks that belong to a target module (the rest is padding: skipped)
+    int nb_live;                    // no longer read (NL is compile-time): kept so that the argument layout stays as it is
 };
 
 constexpr int WG_YP = 128 + 8;      // LDS row pitch of the Y tile (elements): 272 bytes, odd multiple of 16
@@ -213,8 +213,8 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(WgradArgs g) {
 
 using namespace bra;
 
-// tr / nt: adapter rank and targets of the launch (DROP); tr = 32: one target per live block
-static int wgrad_launch(WgradArgs& g, int m_chunk, bool drop, void* stream, int tr = 32, int nt = 0) {
+// s: the table row (bra_lora_plan.h); plain launches take the <RB, 0, RB, RM> form of the same row
+static int wgrad_launch(WgradArgs& g, int m_chunk, bool drop, const LoraSlice& s, void* stream) {
     if (m_chunk <= 0) {
         // enough workgroups to fill the chip twice, at least 256 rows each
         const int ntile = (g.N + 127) / 128;
@@ -226,84 +226,43 @@ static int wgrad_launch(WgradArgs& g, int m_chunk, bool drop, void* stream, int 
     const dim3 grid((g.N + 127) / 128, (g.M + g.m_chunk - 1) / g.m_chunk);
     bra_stream_t st = (bra_stream_t)stream;
     const bool rm = g.c_sn == 1;
-#define BRA_WG(RB_, NL_)                                                                          \
-    do {                                                                                          \
-        if (drop && rm) BRA_LAUNCH((wgrad_tn_kernel<RB_, 1, NL_, 1>), grid, dim3(256), 0, st, g); \
-        else if (drop) BRA_LAUNCH((wgrad_tn_kernel<RB_, 1, NL_, 0>), grid, dim3(256), 0, st, g);  \
-        else if (rm) BRA_LAUNCH((wgrad_tn_kernel<RB_, 0, RB_, 1>), grid, dim3(256), 0, st, g);    \
-        else BRA_LAUNCH((wgrad_tn_kernel<RB_, 0, RB_, 0>), grid, dim3(256), 0, st, g);            \
-    } while (0)
-#define BRA_WGR(RB_, NL_, TR_, NT_)                                                                      \
-    do {                                                                                                 \
-        if (rm) BRA_LAUNCH((wgrad_tn_kernel<RB_, 1, NL_, 1, TR_, NT_>), grid, dim3(256), 0, st, g);      \
-        else BRA_LAUNCH((wgrad_tn_kernel<RB_, 1, NL_, 0, TR_, NT_>), grid, dim3(256), 0, st, g);         \
-    } while (0)
-    if (drop && tr != 32) {
-        if (tr == 8) { if (nt == 1) BRA_WGR(2, 1, 8, 1); else if (nt == 2) BRA_WGR(2, 1, 8, 2); else BRA_WGR(2, 1, 8, 3); }
-        else if (tr == 16) { if (nt == 1) BRA_WGR(2, 1, 16, 1); else if (nt == 2) BRA_WGR(2, 1, 16, 2); else BRA_WGR(2, 2, 16, 3); }
-        else if (tr == 64) { if (g.R == 64) BRA_WGR(2, 2, 64, 1); else BRA_WGR(4, 4, 64, 2); }
-        else BRA_WGR(4, 4, 128, 1);
-    }
-    else if (g.R == 32) BRA_WG(1, 1);
-    else if (g.R == 64) { if (drop && g.nb_live == 1) BRA_WG(2, 1); else BRA_WG(2, 2); }
-    else { if (drop && g.nb_live == 3) BRA_WG(4, 3); else BRA_WG(4, 4); }
-#undef BRA_WGR
+#define BRA_WG(C_, RB_, NL_, TR_, NT_)                                                                             \
+    if (C_) {                                                                                                      \
+        if (drop && rm) BRA_LAUNCH((wgrad_tn_kernel<RB_, 1, NL_, 1, TR_, NT_>), grid, dim3(256), 0, st, g);        \
+        else if (drop) BRA_LAUNCH((wgrad_tn_kernel<RB_, 1, NL_, 0, TR_, NT_>), grid, dim3(256), 0, st, g);         \
+        else if (rm) BRA_LAUNCH((wgrad_tn_kernel<RB_, 0, RB_, 1>), grid, dim3(256), 0, st, g);                     \
+        else BRA_LAUNCH((wgrad_tn_kernel<RB_, 0, RB_, 0>), grid, dim3(256), 0, st, g);                             \
+    } else
+    BRA_LORA_ROWS(BRA_WG) return BRA_ERR_ARG;
 #undef BRA_WG
     return BRA_LAUNCH_STATUS();
+}
+
+// a fused group wider than 128 rank columns (r = 64 x 3 targets: 192, r = 128: 256 / 384): one launch per slice of <= 128 columns
+// of T and C, each with the seeds of its own targets; R <= 128 is the single launch it always was
+static int wgrad_slices(const void* Y, long ldy, const void* T, long ldt, float* C, long c_sn, long c_sr, int M, int N, int R, float alpha,
+                        int m_chunk, bool drop, float p, const unsigned* seeds, int r, int nt, void* stream) {
+    return lora_for_slices(r, nt, R, [&](LoraSlice s) {
+        if (!drop) { s.r = 32; s.nts = s.Rs / 32; }              // no targets: the row of a rank-32 group of this width gives RB
+        WgradArgs g = {(const bf16_t*)Y, ldy, (const bf16_t*)T + s.c0, ldt, C + (long)s.c0 * c_sr, c_sn, c_sr, M, N, s.Rs, 0, alpha,
+                       drop ? make_cfg(p, seeds + s.j0, s.nts) : DropCfg{}, 0};
+        return wgrad_launch(g, m_chunk, drop, s, stream);
+    });
 }
 
 extern "C" int bra_wgrad_tn(const void* Y, long ldy, const void* T, long ldt, float* C, long c_sn, long c_sr, int M, int N,
                             int R, float alpha, int m_chunk, void* stream) {
     if (M == 0 || N == 0) return 0;
     if (!Y || !T || !C || M < 0 || N < 0 || N % 8 || ldy % 8 || ldt % 8 || R <= 0 || (R != 32 && R % 64)) return BRA_ERR_ARG;
-    // a fused group wider than 128 rank columns (r = 64 x 3 targets: 192, r = 128: 256 / 384): one launch per slice of <= 128 columns
-    // of T and C (LDS tile and accumulators hold no more); R <= 128 is the single launch it always was
-    for (int c0 = 0; c0 < R; c0 += 128) {
-        const int Rs = R - c0 < 128 ? R - c0 : 128;
-        WgradArgs g = {(const bf16_t*)Y, ldy, (const bf16_t*)T + c0, ldt, C + (long)c0 * c_sr, c_sn, c_sr, M, N, Rs, 0, alpha, {}, Rs / 32};
-        const int rc = wgrad_launch(g, m_chunk, false, stream);
-        if (rc) return rc;
-    }
-    return 0;
+    return wgrad_slices(Y, ldy, T, ldt, C, c_sn, c_sr, M, N, R, alpha, m_chunk, false, 0.f, nullptr, 0, 0, stream);
 }
 
-// the same with Y masked per rank block: dA of a LoRA branch whose input went through dropout (k_lora.hip)
+// the same with Y masked per target (r, nt: include/bioreason_hip.h): dA of a LoRA branch whose input went through dropout (k_lora.hip)
 extern "C" int bra_wgrad_tn_drop(const void* Y, long ldy, const void* T, long ldt, float* C, long c_sn, long c_sr, int M,
                                  int N, int R, float alpha, int m_chunk, float p, unsigned s0, unsigned s1, unsigned s2,
-                                 unsigned s3, int nb_live, void* stream) {
+                                 unsigned s3, int r, int nt, void* stream) {
     if (M == 0 || N == 0) return 0;
-    if (!Y || !T || !C || M < 0 || N < 0 || N % 8 || ldy % 8 || ldt % 8 || (R != 32 && R != 64 && R != 128)) return BRA_ERR_ARG;
-    if (!(p >= 0.f && p < 1.f) || (long)M * N >= (1l << 32)) return BRA_ERR_ARG;
-    if (nb_live <= 0 || nb_live > R / 32) nb_live = R / 32;
-    WgradArgs g = {(const bf16_t*)Y, ldy, (const bf16_t*)T, ldt, C, c_sn, c_sr, M, N, R, 0, alpha, {}, nb_live};
-    g.d.thr16 = drop_threshold(p);
-    g.d.inv_keep = 1.f / (1.f - p);
-    g.d.seed[0] = s0; g.d.seed[1] = s1; g.d.seed[2] = s2; g.d.seed[3] = s3;
-    return wgrad_launch(g, m_chunk, true, stream);
-}
-
-// bra_wgrad_tn_drop for adapter rank r = 8 / 16 / 32 / 64 / 128 with `nt` <= 3 targets (target j = columns [j r, (j + 1) r) of T,
-// mask stream s_j; R = ceil(nt r / 64) 64); r = 32 is the entry point above.  Groups past 128 columns go slice by slice, each
-// with the seeds of its own targets
-extern "C" int bra_wgrad_tn_drop_r(const void* Y, long ldy, const void* T, long ldt, float* C, long c_sn, long c_sr, int M,
-                                   int N, int R, float alpha, int m_chunk, float p, unsigned s0, unsigned s1, unsigned s2,
-                                   int r, int nt, void* stream) {
-    const bool rank_ok = (r == 8 || r == 16 || r == 32 || r == 64 || r == 128) && nt >= 1 && nt <= 3 && R == (nt * r + 63) / 64 * 64;
-    if (r == 32 && rank_ok) return bra_wgrad_tn_drop(Y, ldy, T, ldt, C, c_sn, c_sr, M, N, R, alpha, m_chunk, p, s0, s1, s2, 0u, nt, stream);
-    if (M == 0 || N == 0) return 0;
-    if (!Y || !T || !C || M < 0 || N < 0 || N % 8 || ldy % 8 || ldt % 8 || !rank_ok) return BRA_ERR_ARG;
-    if (!(p >= 0.f && p < 1.f) || (long)M * N >= (1l << 32)) return BRA_ERR_ARG;
-    const unsigned seeds[3] = {s0, s1, s2};
-    for (int c0 = 0; c0 < R; c0 += 128) {
-        const int Rs = R - c0 < 128 ? R - c0 : 128;
-        const int j0 = r >= 64 ? c0 / r : 0, nts = r >= 64 ? Rs / r : nt;
-        WgradArgs g = {(const bf16_t*)Y, ldy, (const bf16_t*)T + c0, ldt, C + (long)c0 * c_sr, c_sn, c_sr, M, N, Rs, 0, alpha, {},
-                       (nts * r + 31) / 32};
-        g.d.thr16 = drop_threshold(p);
-        g.d.inv_keep = 1.f / (1.f - p);
-        for (int j = 0; j < 4; ++j) g.d.seed[j] = j < nts ? seeds[j0 + j] : 0u;
-        const int rc = wgrad_launch(g, m_chunk, true, stream, r, nts);
-        if (rc) return rc;
-    }
-    return 0;
+    if (!Y || !T || !C || M < 0 || N < 0 || N % 8 || ldy % 8 || ldt % 8 || !lora_drop_ok(p, M, N, r, nt, R)) return BRA_ERR_ARG;
+    const unsigned seeds[4] = {s0, s1, s2, s3};
+    return wgrad_slices(Y, ldy, T, ldt, C, c_sn, c_sr, M, N, R, alpha, m_chunk, true, p, seeds, r, nt, stream);
 }

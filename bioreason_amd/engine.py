@@ -190,9 +190,10 @@ class QwenEngine:
         rest padding)"""
         if x2d.shape[0] < QwenEngine.SMALL_M and A.shape[0] in (32, 64, 128):
             # p = 0: every 32-row block that holds adapter rows is live, whatever the rank (r = 64: one target spans two blocks;
-            # r = 16 x 3 targets: 48 rows in two blocks); the kernel zeroes the blocks past the seeds it is given — the all-padding
-            # blocks (r = 32 x 3 targets in a 128-row image: the fourth) are not multiplied
-            return ops.lora_down_drop(x2d, A, scaling, 0.0, [0] * min(A.shape[0] // 32, (live_rows + 31) // 32))
+            # r = 16 x 3 targets: 48 rows in two blocks), so the image goes as a rank-32 group with one (unused) seed per live block;
+            # the kernel zeroes the blocks past them — the all-padding blocks (r = 32 x 3 targets in a 128-row image: the fourth)
+            # are not multiplied
+            return ops.lora_down_drop(x2d, A, scaling, 0.0, [0] * min(A.shape[0] // 32, (live_rows + 31) // 32), rank=32)
         return ops.gemm_nt(x2d, A, alpha=scaling)
 
     @staticmethod

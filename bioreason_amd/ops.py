@@ -150,34 +150,28 @@ def wgrad_tn(y: torch.Tensor, t: torch.Tensor, out: torch.Tensor, transposed_out
     R = t.shape[1]
     assert t.shape[0] == M and out.dtype == torch.float32 and out.shape == ((R, N) if transposed_out else (N, R))
     c_sn, c_sr = (1, _ld(out)) if transposed_out else (_ld(out), 1)
-    if drop is not None and rank != 32:
-        get_lib().call("bra_wgrad_tn_drop_r", y, _ld(y), t, _ld(t), out, c_sn, c_sr, M, N, R, alpha, m_chunk, drop[0],
-                       *_seeds3(drop[1], rank), rank, len(drop[1]), current_stream(y))
-        return out
     if drop is not None:
         get_lib().call("bra_wgrad_tn_drop", y, _ld(y), t, _ld(t), out, c_sn, c_sr, M, N, R, alpha, m_chunk, drop[0],
-                       *_seeds4(drop[1]), min(len(drop[1]), 4), current_stream(y))
+                       *_group(drop[1], rank, R), current_stream(y))
         return out
     get_lib().call("bra_wgrad_tn", y, _ld(y), t, _ld(t), out, c_sn, c_sr, M, N, R, alpha, m_chunk, current_stream(y))
     return out
 
 
-def _seeds4(seeds):
-    s = [int(x) & 0xFFFFFFFF for x in seeds] + [0, 0, 0, 0]
-    return s[:4]
-
-
 LORA_DROP_RANKS = (8, 16, 32, 64, 128)          # adapter ranks the masked LoRA kernels are built for (k_lora.hip, k_wgrad.hip)
 
 
-def _seeds3(seeds, rank):
-    """(s0, s1, s2) of the bra_*_r entry points: one seed per target module, at most three targets in a fused group"""
+def _group(seeds, rank, R):
+    """(s0, s1, s2, s3, r, nt) of the masked LoRA entry points: one seed per target module.  Rank 32 has one target per 32-column
+    block, so seeds past the group's R // 32 blocks are not used; the other ranks fuse at most three targets"""
     if rank not in LORA_DROP_RANKS:
         raise NotImplementedError(f"LoRA dropout is built for adapter ranks {list(LORA_DROP_RANKS)}, not r = {rank}")
-    if not 1 <= len(seeds) <= 3:
+    if rank == 32:
+        seeds = seeds[:max(R // 32, 1)]
+    elif not 1 <= len(seeds) <= 3:
         raise ValueError(f"a fused LoRA group has 1 to 3 targets, got {len(seeds)} seeds")
-    s = [int(x) & 0xFFFFFFFF for x in seeds] + [0, 0]
-    return s[:3]
+    s = [int(x) & 0xFFFFFFFF for x in seeds]
+    return (*(s + [0, 0, 0, 0])[:4], rank, len(s))
 
 
 def dropout_mask(M: int, K: int, p: float, seed: int, device) -> torch.Tensor:
@@ -198,21 +192,8 @@ def lora_down_drop(x: torch.Tensor, A: torch.Tensor, alpha: float, p: float, see
     t = torch.empty((M, R), dtype=BF16, device=x.device)
     lib = get_lib()
     ks = int(lib._dll.bra_lora_down_splitk_plan(int(M), int(K))) if LORA_DOWN_SPLITK else 1
-    if rank != 32:
-        s3 = _seeds3(seeds, rank)
-        if ks > 1:
-            part = torch.empty((ks, M, R), dtype=torch.float32, device=x.device)
-            lib.call("bra_lora_down_drop_splitk_r", x, _ld(x), A, _ld(A), t, _ld(t), M, K, R, alpha, p, *s3, rank, len(seeds), part, ks,
-                     current_stream(x))
-        else:
-            lib.call("bra_lora_down_drop_r", x, _ld(x), A, _ld(A), t, _ld(t), M, K, R, alpha, p, *s3, rank, len(seeds), current_stream(x))
-        return t
-    if ks > 1:
-        part = torch.empty((ks, M, R), dtype=torch.float32, device=x.device)
-        lib.call("bra_lora_down_drop_splitk", x, _ld(x), A, _ld(A), t, _ld(t), M, K, R, alpha, p, *_seeds4(seeds), min(len(seeds), 4),
-                 part, ks, current_stream(x))
-        return t
-    lib.call("bra_lora_down_drop", x, _ld(x), A, _ld(A), t, _ld(t), M, K, R, alpha, p, *_seeds4(seeds), min(len(seeds), 4),
+    part = torch.empty((ks, M, R), dtype=torch.float32, device=x.device) if ks > 1 else None
+    lib.call("bra_lora_down_drop", x, _ld(x), A, _ld(A), t, _ld(t), M, K, R, alpha, p, *_group(seeds, rank, R), part, ks,
              current_stream(x))
     return t
 
@@ -223,11 +204,7 @@ def lora_up_drop(dts: torch.Tensor, AT: torch.Tensor, p: float, seeds, rank: int
     M, R = dts.shape
     K = AT.shape[0]
     out = torch.empty((M, K), dtype=BF16, device=dts.device)
-    if rank != 32:
-        get_lib().call("bra_lora_up_drop_r", dts, _ld(dts), AT, _ld(AT), out, _ld(out), M, K, R, p, *_seeds3(seeds, rank), rank, len(seeds),
-                       current_stream(dts))
-        return out
-    get_lib().call("bra_lora_up_drop", dts, _ld(dts), AT, _ld(AT), out, _ld(out), M, K, R, p, *_seeds4(seeds), min(len(seeds), 4),
+    get_lib().call("bra_lora_up_drop", dts, _ld(dts), AT, _ld(AT), out, _ld(out), M, K, R, p, *_group(seeds, rank, R),
                    current_stream(dts))
     return out
 

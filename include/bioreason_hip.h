@@ -62,42 +62,33 @@ int bra_wgrad_tn(const void* Y, long ldy, const void* T, long ldt, float* C, lon
 /* LoRA branch under training-mode dropout (k_lora.hip; PEFT: y += (alpha/r) B(A(dropout(x))), lora_dropout 0.05,
  * reason.py:266,376-388).  Every target module of a fused projection has its own mask stream, as PEFT gives every target its
  * own nn.Dropout; keep(seed, m, k) is a hash of the element index m*K + k, so no mask is stored.  M*K < 2^32.
- * Adapter rank 32 (the entry points without _r): a target is one 32-column rank block, streams s0..s3, R in {32, 64, 128}.
  *   bra_lora_down_drop: t[M,R] = alpha * (drop_j(x) A^T)              x [M,K], A [R,K]
  *   bra_lora_up_drop:   out[M,K] = sum_j drop_j'( dts[:, j] A[j, :] )  dts [M,R], AT [K,R]   (input gradient of the branch)
- *   bra_wgrad_tn_drop:  bra_wgrad_tn with Y = drop_rb(Y)               (dA of the branch)
+ *   bra_wgrad_tn_drop:  bra_wgrad_tn with Y = drop_j(Y)                (dA of the branch)
  *   bra_dropout_mask:   out[M,K] bytes = keep(seed, m, k)              (tests: inject the same masks into the oracle)
- * nb_live = rank blocks that belong to a target module (<= R / 32; 0 = all): a fused projection pads its rank to 64 / 128
- * columns, and the padding blocks (zero rows of A, zero columns of dts) are skipped instead of masked. */
-int bra_lora_down_drop(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R, float alpha,
-                       float p, unsigned s0, unsigned s1, unsigned s2, unsigned s3, int nb_live, void* stream);
-/* Split-K form of bra_lora_down_drop for small M (M / 32 row-block workgroups cannot fill 256 CUs and each would read all of A):
- * `ksplit` workgroups per row block take K / ksplit each, fp32 partial tiles go to `part` ([ksplit, M, R] floats, caller-provided)
- * and a second launch sums them in a FIXED order (deterministic) and scales / rounds once.  bra_lora_down_splitk_plan(M, K) returns
- * the split the host layer uses (1 = use the plain form). */
+ * The group (r, nt, R) of all three: adapter rank r in {8, 16, 32, 64, 128} (`lora_r` / `--lora_rank` of the reference scripts), nt
+ * targets; target j owns rank columns [j r, (j + 1) r) and mask stream s_j; R = the group's padded width (the columns past nt r are
+ * padding: zero rows of A, zero columns of dts, zeros in t, skipped instead of masked).
+ *   r = 32:  R in {32, 64, 128}, 1 <= nt <= R / 32, streams s0..s3.  With p = 0 a "target" is just a live 32-row block of A, so
+ *            any image of 32 / 64 / 128 rows goes through here (nt = its blocks that hold adapter rows).
+ *   r != 32: 1 <= nt <= 3, R = ceil(nt r / 64) * 64, s3 ignored.  r >= 64: a target spans r / 32 blocks and its masked operand is
+ *            built once for all of them; r < 32: the 32 / r targets of a block each get their own masked operand.  Groups wider
+ *            than 128 columns (r = 64 x 3, r = 128 x 2 / 3) are walked in slices of <= 128 columns by down and wgrad.
+ * Anything else is BRA_ERR_ARG.
+ * Split-K form of bra_lora_down_drop for small M (M / 32 row-block workgroups cannot fill 256 CUs and each would read all of A):
+ * `ksplit` workgroups per row block take K / ksplit each, fp32 partial tiles go to `part` ([ksplit, M, R] floats, caller-provided;
+ * the tiles of the slice at column c0 start at part + ksplit M c0) and a second launch sums them in a FIXED order (deterministic)
+ * and scales / rounds once.  ksplit <= 1: the plain form, `part` may be null; else `part` is required, ksplit <= ceil(K / 128) and
+ * ldt % 4 == 0.  bra_lora_down_splitk_plan(M, K) returns the split the host layer uses. */
 int bra_lora_down_splitk_plan(int M, int K);
-int bra_lora_down_drop_splitk(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R, float alpha,
-                              float p, unsigned s0, unsigned s1, unsigned s2, unsigned s3, int nb_live, float* part, int ksplit,
-                              void* stream);
+int bra_lora_down_drop(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R, float alpha,
+                       float p, unsigned s0, unsigned s1, unsigned s2, unsigned s3, int r, int nt, float* part, int ksplit,
+                       void* stream);
 int bra_lora_up_drop(const void* dts, long ldd, const void* AT, long ldat, void* out, long ldo, int M, int K, int R, float p,
-                     unsigned s0, unsigned s1, unsigned s2, unsigned s3, int nb_live, void* stream);
+                     unsigned s0, unsigned s1, unsigned s2, unsigned s3, int r, int nt, void* stream);
 int bra_wgrad_tn_drop(const void* Y, long ldy, const void* T, long ldt, float* C, long c_sn, long c_sr, int M, int N, int R,
-                      float alpha, int m_chunk, float p, unsigned s0, unsigned s1, unsigned s2, unsigned s3, int nb_live,
+                      float alpha, int m_chunk, float p, unsigned s0, unsigned s1, unsigned s2, unsigned s3, int r, int nt,
                       void* stream);
-/* The same for adapter rank r in {8, 16, 32, 64, 128} (`lora_r` / `--lora_rank` of the reference scripts) and nt <= 3 targets:
- * target j owns rank columns [j r, (j + 1) r) and mask stream s_j; R = ceil(nt r / 64) * 64 (the fused group's padded width; the
- * columns past nt r are padding: zeros in t, never masked).  r >= 64: a target spans r / 32 blocks and its masked operand is built
- * once for all of them; r < 32: the 32 / r targets of a block each get their own masked operand.  Groups wider than 128 columns
- * (r = 64 x 3, r = 128 x 2 / 3) are walked in slices of <= 128 columns by down and wgrad.  r = 32 forwards to the entry points
- * above.  `part` of the split-K form: [ksplit, M, R] floats. */
-int bra_lora_down_drop_r(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R, float alpha,
-                         float p, unsigned s0, unsigned s1, unsigned s2, int r, int nt, void* stream);
-int bra_lora_down_drop_splitk_r(const void* x, long ldx, const void* A, long lda, void* t, long ldt, int M, int K, int R, float alpha,
-                                float p, unsigned s0, unsigned s1, unsigned s2, int r, int nt, float* part, int ksplit, void* stream);
-int bra_lora_up_drop_r(const void* dts, long ldd, const void* AT, long ldat, void* out, long ldo, int M, int K, int R, float p,
-                       unsigned s0, unsigned s1, unsigned s2, int r, int nt, void* stream);
-int bra_wgrad_tn_drop_r(const void* Y, long ldy, const void* T, long ldt, float* C, long c_sn, long c_sr, int M, int N, int R,
-                        float alpha, int m_chunk, float p, unsigned s0, unsigned s1, unsigned s2, int r, int nt, void* stream);
 int bra_dropout_mask(void* out, int M, int K, float p, unsigned seed, void* stream);
 
 /* Fused lm_head + log-softmax statistics WITHOUT materialising logits

@@ -1197,7 +1197,7 @@ def test_lora_dropout_kernels(backend, M, K, R):
 @pytest.mark.parametrize("M,K,R,nlive", [(100, 768, 64, 2), (70, 1024, 128, 3), (33, 896, 32, 1), (40, 6144, 64, 1)])
 def test_lora_down_drop_split_k(backend, M, K, R, nlive):
     """small M: `ksplit` workgroups per 32-row block take K / ksplit each, a second launch sums the fp32 partial tiles in a fixed order
-    (bra_lora_down_drop_splitk) — same masks (the hash is of the element index), same result up to the fp32 summation order,
+    (bra_lora_down_drop with ksplit > 1) — same masks (the hash is of the element index), same result up to the fp32 summation order,
     deterministic from call to call"""
     from bioreason_amd._lib import get_lib
     p, seeds = 0.25, [11, 22, 33, 44][:nlive]

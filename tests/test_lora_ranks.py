@@ -13,7 +13,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from bioreason_amd import ops                            # noqa: E402
-from bioreason_amd._lib import current_stream, get_lib  # noqa: E402
+from bioreason_amd._lib import BRA_ERR_ARG, KernelError, current_stream, get_lib  # noqa: E402
 
 BF = torch.bfloat16
 
@@ -32,8 +32,8 @@ def r_pad(r, targets):
     return (targets * r + 63) // 64 * 64                 # engine.LoraGroup
 
 
-RANK_CASES = [(8, 1), (8, 3), (16, 2), (16, 3), (32, 3), (64, 1), (64, 3), (128, 2), (128, 3)]
-P, SEEDS = 0.25, [5, 6, 7]
+RANK_CASES = [(8, 1), (8, 3), (16, 2), (16, 3), (32, 1), (32, 2), (32, 3), (32, 4), (64, 1), (64, 3), (128, 2), (128, 3)]
+P, SEEDS = 0.25, [5, 6, 7, 8]
 
 
 def _operands(r, targets, M, K, dev):
@@ -85,31 +85,6 @@ def test_lora_dropout_kernels_at_every_rank(backend, r, targets):
     assert rel(dA, _want_dA(dts, xd, r, targets, K)) < 1e-5 and (dA[targets * r:] == 0).all()
 
 
-def test_rank_32_through_the_rank_entry_points_is_the_old_kernels(backend):
-    """(32, 3): bra_*_r with r = 32 reach the instantiations of the entry points without _r — equal bit for bit"""
-    M, K, r, targets = 97, 136, 32, 3
-    x, A, dts, _, _ = _operands(r, targets, M, K, backend)
-    R, AT = A.shape[0], A.T.contiguous()
-    lib, st = get_lib(), current_stream(x)
-    t_old = ops.lora_down_drop(x, A, 0.5, P, SEEDS)
-    t_new = torch.empty_like(t_old)
-    lib.call("bra_lora_down_drop_r", x, K, A, K, t_new, R, M, K, R, 0.5, P, *SEEDS, r, targets, st)
-    assert torch.equal(t_old.cpu(), t_new.cpu())
-    part = torch.empty((2, M, R), dtype=torch.float32, device=backend)
-    t_sk_old, t_sk_new = torch.empty_like(t_old), torch.empty_like(t_old)
-    lib.call("bra_lora_down_drop_splitk", x, K, A, K, t_sk_old, R, M, K, R, 0.5, P, *SEEDS, 0, targets, part, 2, st)
-    lib.call("bra_lora_down_drop_splitk_r", x, K, A, K, t_sk_new, R, M, K, R, 0.5, P, *SEEDS, r, targets, part, 2, st)
-    assert torch.equal(t_sk_old.cpu(), t_sk_new.cpu())
-    up_old = ops.lora_up_drop(dts, AT, P, SEEDS)
-    up_new = torch.empty_like(up_old)
-    lib.call("bra_lora_up_drop_r", dts, R, AT, R, up_new, K, M, K, R, P, *SEEDS, r, targets, st)
-    assert torch.equal(up_old.cpu(), up_new.cpu())
-    dA_old, dA_new = torch.zeros(R, K, device=backend), torch.zeros(R, K, device=backend)
-    ops.wgrad_tn(x, dts, dA_old, transposed_out=True, drop=(P, SEEDS))      # one row chunk: one atomic per element, onto zero
-    lib.call("bra_wgrad_tn_drop_r", x, K, dts, R, dA_new, 1, K, M, K, R, 1.0, 0, P, *SEEDS, r, targets, st)
-    assert torch.equal(dA_old.cpu(), dA_new.cpu())
-
-
 @pytest.mark.parametrize("r,targets", RANK_CASES)
 def test_lora_down_drop_split_k_at_every_rank(backend, r, targets):
     """K = 776 at M = 97: bra_lora_down_splitk_plan says 2, so the split-K form runs (fp32 partial tiles per slice of the group, summed in
@@ -144,6 +119,36 @@ def test_ranks_without_a_masked_kernel_are_refused(backend):
     x, A = rnd(8, 64, dev=backend), rnd(128, 64, dev=backend)
     with pytest.raises(NotImplementedError, match="128"):
         ops.lora_down_drop(x, A, 1.0, 0.1, [1, 2, 3], rank=40)
+
+
+def test_group_descriptions_outside_the_contract_are_refused(backend):
+    """the C entry points themselves (include/bioreason_hip.h: r in {8, 16, 32, 64, 128}; r = 32: 1 <= nt <= R / 32; otherwise
+    1 <= nt <= 3 and R = ceil(nt r / 64) 64; split-K needs `part`): BRA_ERR_ARG from all three, and nothing is launched — the outputs
+    keep their fill"""
+    M, K = 8, 256
+    lib, st = get_lib(), current_stream(None)
+
+    def status(name, *args):
+        try:
+            return lib.call(name, *args)
+        except KernelError as e:
+            return e.status
+    for r, nt, R in [(32, 0, 64), (32, 3, 64), (16, 4, 64), (64, 3, 128), (40, 1, 64)]:
+        x, A, dts = rnd(M, K, dev=backend), rnd(R, K, dev=backend), rnd(M, R, dev=backend)
+        t, up = torch.full((M, R), 7.0, dtype=BF, device=backend), torch.full((M, K), 7.0, dtype=BF, device=backend)
+        dA = torch.full((R, K), 7.0, device=backend)
+        part = torch.full((2, M, R), 7.0, device=backend)
+        for ks in (1, 2):
+            assert status("bra_lora_down_drop", x, K, A, K, t, R, M, K, R, 0.5, P, *SEEDS, r, nt, part, ks, st) == BRA_ERR_ARG, (r, nt, R)
+        assert status("bra_lora_up_drop", dts, R, A.T.contiguous(), R, up, K, M, K, R, P, *SEEDS, r, nt, st) == BRA_ERR_ARG, (r, nt, R)
+        assert status("bra_wgrad_tn_drop", x, K, dts, R, dA, 1, K, M, K, R, 1.0, 0, P, *SEEDS, r, nt, st) == BRA_ERR_ARG, (r, nt, R)
+        assert (t == 7).all() and (up == 7).all() and (dA == 7).all() and (part == 7).all()
+    # a valid group (32 x 2 in 64 columns; ksplit = 2 <= ceil(K / 128)), split-K without the partial tiles
+    x, A, t = rnd(M, K, dev=backend), rnd(64, K, dev=backend), torch.full((M, 64), 7.0, dtype=BF, device=backend)
+    assert status("bra_lora_down_drop", x, K, A, K, t, 64, M, K, 64, 0.5, P, *SEEDS, 32, 2, None, 2, st) == BRA_ERR_ARG
+    assert (t == 7).all()
+    assert status("bra_lora_down_drop", x, K, A, K, t, 64, M, K, 64, 0.5, P, *SEEDS, 32, 2, None, 1, st) == 0     # the plain form
+    assert not (t == 7).all()
 
 
 # ----------------------------------------------------------------------------- 2. the plain branch past 128 rank columns

@@ -23,6 +23,6 @@ for M in (17440, 19488, 2180):
             for ks in (1, 2, 3, 4, 6):
                 part = torch.empty((ks, M, R), dtype=torch.float32, device=dev)
                 def run():
-                    lib.call("bra_lora_down_drop_splitk", x, K, A, K, t, R, M, K, R, 2.0, p, *seeds, nt, part, ks, current_stream(x))
+                    lib.call("bra_lora_down_drop", x, K, A, K, t, R, M, K, R, 2.0, p, *seeds, 32, nt, part, ks, current_stream(x))
                 res[(p, ks)] = timeit(run)
         print(f"M {M:6d} {name:8s} K {K} R {R}: " + "  ".join(f"p={p} ks={ks}: {v:5.1f}us" for (p, ks), v in res.items()), flush=True)
