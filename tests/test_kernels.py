@@ -6,6 +6,9 @@ gfx950 library (`-m gpu`).  Inputs are bf16; tolerances are those of one bf16 ro
 
 Attention (prefill / training): the global bounds here are the coarse check; tests/test_attn_rowwise.py holds every output row
 against a float64 reference and its own rounding bound, at adversarial values, strided layouts and the step's own shapes.
+The loss path (lmhead_logprob, grpo_loss, lmhead_dlogits, gemm_nt with E^T) and group_advantage / eos_mask likewise: the bounds
+here are the coarse check; tests/test_loss_path_rowwise.py holds every row (every element, on exact logits) against float64, with
+targets placed on the chunk, fragment and ragged-tail columns of the epilogues, on every GEMM kernel the dispatch can take.
 """
 import math
 
