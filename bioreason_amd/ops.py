@@ -423,6 +423,43 @@ def attn_decode(q, kc, vc, kmask, length: int, scale: float, ws=None):
     return o
 
 
+# --------------------------------------------------------------------------- attention pooling (DNA-only classifier)
+def _pool_args(x: torch.Tensor, mask: torch.Tensor, qt: torch.Tensor):
+    n, S, H = x.shape
+    assert x.dtype == BF16 and x.stride(2) == 1 and qt.dtype == torch.float32 and qt.is_contiguous() and qt.shape[1] == H
+    assert mask.dtype == torch.uint8 and mask.shape == (n, S) and mask.is_contiguous()
+    return n, S, H, qt.shape[0]
+
+
+def attn_pool_fwd(x: torch.Tensor, mask: torch.Tensor, qt: torch.Tensor, chunk: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x [n, S, H] bf16 (rows may be strided), mask [n, S] u8 (1 = valid key), qt [8, H] fp32 -> pooled [n, 8, H] fp32 =
+    sum_l softmax_l(x_l . qt_h) x_l and lse [n, 8] fp32; `chunk` = rows per workgroup (0: the library's choice)"""
+    n, S, H, NH = _pool_args(x, mask, qt)
+    lib = get_lib()
+    ns = max(1, int(lib._dll.bra_attn_pool_nsplit(int(n), int(S), int(chunk))))
+    pooled = torch.empty((n, NH, H), dtype=torch.float32, device=x.device)
+    lse = torch.empty((n, NH), dtype=torch.float32, device=x.device)
+    part_acc = torch.empty((n, ns, NH, H), dtype=torch.float32, device=x.device)
+    part_ml = torch.empty((n, ns, NH, 2), dtype=torch.float32, device=x.device)
+    lib.call("bra_attn_pool_fwd", x, x.stride(0), x.stride(1), mask, qt, pooled, lse, part_acc, part_ml, n, S, H, NH, chunk,
+             current_stream(x))
+    return pooled, lse
+
+
+def attn_pool_bwd(x: torch.Tensor, mask: torch.Tensor, qt: torch.Tensor, pooled: torch.Tensor, lse: torch.Tensor, g: torch.Tensor,
+                  chunk: int = 0) -> torch.Tensor:
+    """gradient of attn_pool_fwd with respect to qt for the upstream gradient g [n, 8, H] fp32 of `pooled` (x is frozen): [8, H] fp32"""
+    n, S, H, NH = _pool_args(x, mask, qt)
+    assert g.dtype == torch.float32 and g.shape == pooled.shape == (n, NH, H) and g.is_contiguous() and pooled.is_contiguous()
+    lib = get_lib()
+    ns = max(1, int(lib._dll.bra_attn_pool_nsplit(int(n), int(S), int(chunk))))
+    part = torch.empty((n, ns, NH, H), dtype=torch.float32, device=x.device)
+    dqt = torch.empty((NH, H), dtype=torch.float32, device=x.device)
+    lib.call("bra_attn_pool_bwd", x, x.stride(0), x.stride(1), mask, qt, pooled, lse, g, dqt, part, n, S, H, NH, chunk,
+             current_stream(x))
+    return dqt
+
+
 # --------------------------------------------------------------------------- data movement
 def dna_scatter_plan(ids32, dna_id, dna_mask_u8, seq_order, tok_src, counts):
     nseq, Sd = (dna_mask_u8.shape if dna_mask_u8 is not None else (0, 0))

@@ -430,6 +430,24 @@ int bra_group_sum(const void* src, long member_stride, int copies, const void* a
 int bra_group_broadcast(const void* src, long src_blk_stride, void* out, long out_blk_stride, int R, int copies, int inner, long n,
                         void* stream);
 
+/* ---- attention pooling (k_pool.hip) ---------------------------------------------
+ * SelfAttentionPooling of the DNA-only classifier (bioreason/models/dna_only.py:8-39: nn.MultiheadAttention with ONE learned query,
+ * 8 heads, key_padding_mask) with the K / V projections folded into the query (DESIGN.md "Attention pooling"): the data-sized work
+ * is one pass over the hidden states.  x bf16 [n, S, H] (element strides x_sb, x_ss, multiples of 8; H contiguous), mask bytes
+ * [n, S] (1 = valid key, any pattern), qt fp32 [NH, H] = scale W_k,h^T q_h.
+ *   forward : pooled fp32 [n, NH, H] = sum_l softmax_l(x_l . qt_h) x_l, lse fp32 [n, NH]; a sequence without a valid key gets NaN
+ *   backward: dqt fp32 [NH, H] = sum_{n, l} p (x_l . g_h - pooled_h . g_h) x_l, g fp32 [n, NH, H] = d loss / d pooled (x is frozen)
+ * S is split over workgroups in chunks of `chunk` rows (rounded up to 128; 0: chosen to fill the chip), nsplit =
+ * bra_attn_pool_nsplit(n, S, chunk) chunks per sequence; the partials (part_acc / part: fp32 [n, nsplit, NH, H], part_ml: fp32
+ * [n, nsplit, NH, 2], caller-owned) are combined by a second launch in a fixed order: no atomics, bit-repeatable.
+ * NH = 8, H % 64 == 0, H <= 2048 (NT-v2 512 / 768 / 1024, Evo2-1B 1920); BRA_ERR_UNSUPPORTED otherwise. */
+int bra_attn_pool_nsplit(int n, int S, int chunk);
+int bra_attn_pool_fwd(const void* x, long x_sb, long x_ss, const void* mask, const float* qt, float* pooled, float* lse,
+                      float* part_acc, float* part_ml, int n, int S, int H, int NH, int chunk, void* stream);
+int bra_attn_pool_bwd(const void* x, long x_sb, long x_ss, const void* mask, const float* qt, const float* pooled,
+                      const float* lse, const float* g, float* dqt, float* part, int n, int S, int H, int NH, int chunk,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
