@@ -23,6 +23,12 @@ namespace bra {
 // fragments in registers for all tiles, request tile i+1's weights before multiplying tile i, and hand the K-reduction
 // and epilogue of tile i to wave i % NW through a double-buffered LDS slab (one barrier per tile).
 // WIDE: 9 .. 16 batch rows (two prompts x 8 rollouts per GPU): MODE 0 only (the diagonal tiles hold 8 rows), folded norm or none
+// WIDE == 2: 17 .. 32 batch rows (three or four prompts x 8 rollouts): the weight fragment of a (tile, k-step) is requested once, as
+// in the 16-row form, and feeds TWO MFMAs — against the activation fragments of rows 0 - 15 and of rows 16 - 31 — into two
+// accumulators.  Per output element the K-reduction is the 16-row form's own (same k-steps per wave, same wave order in the LDS
+// hand-off, same fold of the statistics), so row r of a 32-row launch is bit-identical to row r of a 16-row launch on the same
+// inputs.  The two row halves of a tile are finished by two different waves (i % NW and (i + 1) % NW), each through the unchanged
+// 16-row epilogue on a record whose row pointers are moved down 16 rows.
 // PK: the weights are in fragment order (compile-time: with a run-time flag every weight address is built both ways and selected,
 // ~100 VALU instructions between kernel entry and the first weight request of a launch that lasts 5-11 us)
 // FAST (the shapes of the decode step): packed weights, K == NW * NL * KS exactly (one register round, no step is clamped or
@@ -44,11 +50,23 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
     // 5 - 10 us launch otherwise waits for before it can form its first address)
     DecGemm2Args g = g0;
     g.x = h_x; g.W = h_W; g.res = h_res; g.ss_in = h_ss_in; g.ldx = h_ldx; g.ldres = h_ldres; g.M = h_M; g.N = h_N; g.K = h_K; g.nss_in = h_nss_in;
+    // WIDE == 3: the 32-row form of the multi-round loop alone (K beyond one register round) — a kernel of its own, so that neither
+    // path pays for the other's registers
+    constexpr bool W32 = WIDE >= 2;
+    static_assert(WIDE != 3 || (!FAST && NORM == 0), "32 rows, multi-round: not the fast form, no folded norm");
     static_assert(!WIDE || (MODE == 0 && NORM != 1), "wide rows: 16-column tiles, statistics applied in the epilogue");
     static_assert(!FAST || (PK && NORM != 1), "fast form: packed weights, folded norm or none");
     static_assert(!F8 || (FAST && NL % 2 == 0 && NW != 16 && !WIDE), "fp8 weights: fast form, two k-steps per 16-byte request");
+    static_assert(WIDE != 2 || !F8, "32 rows: bf16 weights");
     constexpr int NLW = F8 ? NL / 2 : NL;                               // 16-byte weight requests per lane and tile
-    __shared__ float red[2][NW][64][4];
+    constexpr int NH = W32 ? 2 : 1;                               // 16-row halves of the batch (slab rows [h * NW, (h + 1) * NW))
+    // (32 rows x 16 waves: one slab — 64 KiB of LDS would hold two; the single-round form of 16 waves runs one tile per workgroup,
+    //  the multi-round loop pays a second barrier per tile)
+    // INVARIANT (launch_dg2: `gmax = nw == 16 ? ntiles : ..`): the single-round form of 16 waves gets one workgroup per tile — it
+    // reuses x[] for rows 16 .. 31 and has one slab, both wrong for a second tile; the multi-round loop re-reads x and pays the
+    // second barrier, so it may walk several tiles
+    constexpr int NBUF = (W32 && NW == 16) ? 1 : 2;
+    __shared__ float red[NBUF][NH * NW][64][4];
     constexpr int KS = MODE ? 64 : 32;
     constexpr int NCOL = MODE ? 8 : 16;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -60,6 +78,21 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
     const int koff = MODE ? ((fr >> 3) * 32 + fq * 8) : fq * 8;
     const int xr = lrow < g.M ? lrow : g.M - 1;
     const bf16_t* xp = FAST ? g.x + (dg2_mul24(xr, (int)g.ldx) + (unsigned)koff) : g.x + (long)xr * g.ldx + koff;
+    // rows 16 .. 31 (W32): clamped like the first half — a row past M re-reads row M - 1 and is never stored.  Everything
+    // the second half needs is formed BEHIND the weight requests: the path from kernel entry to the first request stays the
+    // 16-row form's
+    auto x2_ptr = [&]() -> const bf16_t* {
+        const int xr2 = lrow + 16 < g.M ? lrow + 16 : g.M - 1;
+        return FAST ? g.x + (dg2_mul24(xr2, (int)g.ldx) + (unsigned)koff) : g.x + (long)xr2 * g.ldx + koff;
+    };
+    auto second_half = [&]() -> DecGemm2Args {        // the record the second half's epilogue sees: the same tile, 16 rows down
+        DecGemm2Args g2 = g;
+        g2.M = g.M - 16;
+        if (g.res) g2.res = g.res + 16 * g.ldres;
+        g2.out = OUTF32 ? (void*)((float*)g.out + 16 * g.ldo) : (void*)((bf16_t*)g.out + 16 * g.ldo);
+        if (g.ss_out) g2.ss_out = g.ss_out + 16 * (long)g.nss_out;
+        return g2;
+    };
     const u32x4 zero4 = {0u, 0u, 0u, 0u};
     const int rounds = FAST ? 1 : (nsteps + NW * NL - 1) / (NW * NL);
     int tile = (int)blockIdx.x;
@@ -69,8 +102,9 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
     // epilogue operand of the first tile requested now (all waves, clamped address: no branch around a load)
     const int em = fr < g.M ? fr : g.M - 1;
     int en = tile * NCOL + 4 * fq; en = en + 3 < g.N ? en : (g.N >= 4 ? g.N - 4 : 0);
-    u32x2 resv = {0u, 0u};
+    u32x2 resv = {0u, 0u}, resv2 = {0u, 0u};
     if (!FAST && !ACT && !OUTF32 && g.res) resv = ld8(g.res + (long)em * g.ldres + en);
+    auto em2_row = [&]() -> int { return fr + 16 < g.M ? fr : g.M - 17; };      // row of the second half's record (formed where it is used)
 
     // NORM: lane l folds partials [per * (l & 7), per * (l & 7) + per) of row l >> 3 (per <= 32, fixed order =>
     // run-to-run identical); requested first, they are the smallest and the first thing the MFMAs need
@@ -80,7 +114,7 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
     // NORM == 1 are 3x the weight bytes); wave 0 alone folds the statistics, behind its weight requests, into LDS.
     const int per = NORM ? g.nss_in >> 3 : 0;
     f32x4 pv[8];
-    __shared__ float rs_lds[WIDE ? 16 : 8];
+    __shared__ float rs_lds[W32 ? 32 : (WIDE ? 16 : 8)];
     if (NORM == 1) {
         const float* pp = g.ss_in + (long)(lane >> 3) * g.nss_in + (lane & 7) * per;
 #pragma unroll
@@ -88,7 +122,7 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
     }
     float rstd = 1.f;
 
-    if (rounds == 1) {
+    if (WIDE != 3 && rounds == 1) {
         int st[NL];
 #pragma unroll
         for (int u = 0; u < NL; ++u)      // MODE 0: a wave takes both 64-byte halves of a 128-byte line back to back;
@@ -100,7 +134,10 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
         if (FAST) xp += (unsigned)(wave * (NL * KS));
         // request order = arrival order (one in-order counter per wave): statistics, activations, norm weights, then
         // the weight tile, so that the normalisation below runs while the weights are still in flight
-        u32x4 w0[NLW], w1[NLW], x[NL], nv[NL];
+        // (X2LATE — 32 rows on 16 waves, 128 registers per lane: the fragments of rows 16 .. 31 take the registers of rows 0 .. 15
+        //  once the first half's MFMAs have read them; that form runs one tile per workgroup, so nothing is re-read)
+        constexpr bool X2LATE = W32 && NW == 16;
+        u32x4 w0[NLW], w1[NLW], x[NL], nv[NL], x2[(W32 && !X2LATE) ? NL : 1];
         f32x4 sc0 = {1.f, 1.f, 1.f, 1.f}, sc1 = sc0;                      // F8: scales of the four weight rows behind this lane's products
 #pragma unroll
         for (int u = 0; u < NL; ++u) x[u] = ld16(xp + so[u]);
@@ -127,7 +164,23 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
         };
         wp = tile_base(tile);
 #pragma unroll
-        for (int u = 0; u < NLW; ++u) w0[u] = ld16_nt(wp + wo[u]);
+        for (int u = 0; u < NLW; ++u) {
+            w0[u] = ld16_nt(wp + wo[u]);
+            // (32 rows: under the higher register pressure the scheduler otherwise forms the bases of the requests past the
+            //  4 KiB immediate range first — 7 - 8 instructions in front of the first request)
+            if (W32 && u == 0) sched_fence();
+        }
+        const bf16_t* xp2 = xp;
+        if constexpr (W32) {
+            sched_fence();                // the weight requests are out: now the second half's activations
+            xp2 = x2_ptr();
+            if (FAST) xp2 += (unsigned)(wave * (NL * KS));
+            if constexpr (!X2LATE) {
+#pragma unroll
+                for (int u = 0; u < NL; ++u) x2[u] = ld16(xp2 + so[u]);
+            }
+            if (!FAST && !ACT && !OUTF32 && g.res) resv2 = ld8(g.res + (long)(em2_row() + 16) * g.ldres + en);
+        }
         if (F8) {
             sched_fence();                // the weight requests go out before anything waits for the scale pointer (argument segment)
             sc0 = scale_of(tile);
@@ -136,18 +189,20 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
             const bf16_t* rp = g.res ? g.res : g.x;
             const unsigned ro = g.res ? dg2_mul24(em, (int)g.ldres) + (unsigned)en : 0u;
             resv = ld8(rp + ro);
+            if (W32) resv2 = ld8(rp + (g.res ? dg2_mul24(em2_row() + 16, (int)g.ldres) + (unsigned)en : 0u));
         }
         sched_fence();                    // every request above is in flight before the first dependent instruction
         if (!FAST) dg2_stamp(g, 1);
         // folded norm: wave 0 requests the statistics partials behind its weights — all of them, unconditionally (a load that
         // sits under a uniform `4 i < per` test is issued and awaited one at a time: eight serial round trips on the wave
         // that every other wave then waits for at the first barrier) — and folds them in the shadow of the first tile's MFMAs
-        constexpr int NPASS = WIDE ? 2 : 1;
+        constexpr int NPASS = WIDE == 1 ? 2 : 1;          // (32 rows: waves 0 .. 3 fold eight rows each — 32 registers instead of 64)
         f32x4 sq[NPASS][8];
-        if (NORM == 2 && wave == 0) {
+        const int swave = W32 ? 4 : 1, sbase = W32 ? 8 * wave : 0;
+        if (NORM == 2 && wave < swave) {
 #pragma unroll
             for (int pass = 0; pass < NPASS; ++pass) {
-                const int srow = (lane >> 3) + 8 * pass;                                    // (rows past M fold row M - 1 again)
+                const int srow = (lane >> 3) + 8 * pass + sbase;                            // (rows past M fold row M - 1 again)
                 const int sr = srow < g.M ? srow : g.M - 1;
                 const float* pp = FAST ? g.ss_in + (dg2_mul24(sr, g.nss_in) + (unsigned)((lane & 7) * per))
                                        : g.ss_in + (long)sr * g.nss_in + (lane & 7) * per;
@@ -162,7 +217,7 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
         auto fold_stats = [&]() {
 #pragma unroll
             for (int pass = 0; pass < NPASS; ++pass) {
-                const int srow = (lane >> 3) + 8 * pass;
+                const int srow = (lane >> 3) + 8 * pass + sbase;
                 const float rs = dg2_fold_rstd(sq[pass], per, g.inv_K, g.eps);
                 if ((lane & 7) == 0) rs_lds[srow] = rs;       // visible after the tile barrier
             }
@@ -186,6 +241,10 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
         }
 #pragma unroll
         for (int u = 0; u < NL; ++u) if (!FAST && st[u] >= nsteps) x[u] = zero4;        // steps past K contribute zero
+        if constexpr (W32 && !X2LATE) {
+#pragma unroll
+            for (int u = 0; u < NL; ++u) if (!FAST && st[u] >= nsteps) x2[u] = zero4;
+        }
         // weight registers ping-pong (w0 / w1): tile i+1 is requested before tile i is multiplied.  The requests sit
         // in straight-line code (no branch around a load: the compiler would wait for them at the join), so the last
         // one or two tiles are peeled.
@@ -209,10 +268,27 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
 #pragma unroll
                 for (int u = 0; u < NL; ++u) acc = mfma_16x16x32(wc[u], x[u], acc);
             }
-            if (NORM == 2 && it == 0 && wave == 0) fold_stats();
-            float (*slab)[64][4] = red[it & 1];
+            f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (X2LATE) {
+                sched_fence();
+#pragma unroll
+                for (int u = 0; u < NL; ++u) x[u] = ld16(xp2 + so[u]);
+#pragma unroll
+                for (int u = 0; u < NL; ++u) if (!FAST && st[u] >= nsteps) x[u] = zero4;
+#pragma unroll
+                for (int u = 0; u < NL; ++u) acc2 = mfma_16x16x32(wc[u], x[u], acc2);
+            } else if constexpr (W32) {
+#pragma unroll
+                for (int u = 0; u < NL; ++u) acc2 = mfma_16x16x32(wc[u], x2[u], acc2);
+            }
+            if (NORM == 2 && it == 0 && wave < swave) fold_stats();
+            float (*slab)[64][4] = red[NBUF == 2 ? it & 1 : 0];
 #pragma unroll
             for (int r = 0; r < 4; ++r) slab[wave][lane][r] = acc[r];
+            if constexpr (W32) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) slab[NW + wave][lane][r] = acc2[r];
+            }
             if (!FAST && it == 0) dg2_stamp(g, 2);
             __syncthreads();
             if (!FAST && it == 0) dg2_stamp(g, 3);
@@ -230,6 +306,19 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
                     for (int r = 0; r < 4; ++r) v[r] *= scc[r];
                 }
                 dg2_epilogue<MODE, ACT, OUTF32, PK>(g, v, t, lane, it == 0, resv);
+            }
+            if constexpr (W32) {
+                if (wave == (it + 1) % NW) {          // rows 16 .. 31: the same reduction and epilogue, on the next wave
+                    float v[4];
+                    dg2_reduce<NW>(slab + NW, lane, v);
+                    if (NORM == 2) {
+                        const float rsf = rs_lds[16 + em2_row()];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] *= rsf;
+                    }
+                    const DecGemm2Args g2 = second_half();
+                    dg2_epilogue<MODE, ACT, OUTF32, PK>(g2, v, t, lane, it == 0, resv2);
+                }
             }
             if (!FAST && it == 0) dg2_stamp(g, 4);
         };
@@ -251,17 +340,21 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
         return;
     }
 
+    if constexpr (WIDE == 2) return;      // (32 rows: the host launches the multi-round loop as its own kernel, WIDE == 3)
     // K larger than one register round (NW * NL steps): one tile per iteration, fragments re-read every round
+    // (32 rows on 16 waves, 128 registers per lane: the fragments of rows 16 .. 31 take the registers of rows 0 .. 15 once the round's
+    //  first-half MFMAs have read them, as in the single-round form; x is re-read every round here anyway)
+    constexpr bool X2LATE_MR = W32 && NW == 16;
     for (int it = 0; tile < ntiles; ++it, tile += (int)gridDim.x) {
         rn = tile * NCOL + lrow; rn = rn < g.N ? rn : g.N - 1;
         wp = g.W + (long)rn * g.ldw + koff;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc2 = acc;
         for (int rd = 0; rd < rounds; ++rd) {
             const int base = rd * NW * NL;
             int st[NL];
 #pragma unroll
             for (int u = 0; u < NL; ++u) st[u] = base + (MODE ? wave + NW * u : 2 * (wave + NW * (u >> 1)) + (u & 1));
-            u32x4 w[NL], x[NL], nv[NL];
+            u32x4 w[NL], x[NL], nv[NL], x2[(W32 && !X2LATE_MR) ? NL : 1];
             // (packed weights: chunk ((tile * nsteps + step) * 64 + lane) holds the lane's 8 elements of (tile, step) — K beyond one
             //  register round, e.g. Qwen3-4B's o / down projections, walks the same image round by round)
             const bf16_t* wpk = g.W + ((long)tile * nsteps * 64 + lane) * 8;
@@ -272,6 +365,16 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
             }
 #pragma unroll
             for (int u = 0; u < NL; ++u) { const int sc = st[u] < nsteps ? st[u] : nsteps - 1; x[u] = ld16(xp + (long)sc * KS); }
+            const bf16_t* xp2 = xp;
+            if constexpr (W32) {
+                sched_fence();            // weights and first-half activations are requested: now what the second half needs
+                xp2 = x2_ptr();
+                if (it == 0 && rd == 0 && !ACT && !OUTF32 && g.res) resv2 = ld8(g.res + (long)(em2_row() + 16) * g.ldres + en);
+                if constexpr (!X2LATE_MR) {
+#pragma unroll
+                    for (int u = 0; u < NL; ++u) { const int sc = st[u] < nsteps ? st[u] : nsteps - 1; x2[u] = ld16(xp2 + (long)sc * KS); }
+                }
+            }
             if (NORM == 1) {
 #pragma unroll
                 for (int u = 0; u < NL; ++u) { const int sc = st[u] < nsteps ? st[u] : nsteps - 1; nv[u] = ld16(g.nw + koff + (long)sc * KS); }
@@ -293,10 +396,24 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
             }
 #pragma unroll
             for (int u = 0; u < NL; ++u) acc = mfma_16x16x32(st[u] < nsteps ? w[u] : zero4, x[u], acc);
+            if constexpr (X2LATE_MR) {
+                sched_fence();
+#pragma unroll
+                for (int u = 0; u < NL; ++u) { const int sc = st[u] < nsteps ? st[u] : nsteps - 1; x[u] = ld16(xp2 + (long)sc * KS); }
+#pragma unroll
+                for (int u = 0; u < NL; ++u) acc2 = mfma_16x16x32(st[u] < nsteps ? w[u] : zero4, x[u], acc2);
+            } else if constexpr (W32) {
+#pragma unroll
+                for (int u = 0; u < NL; ++u) acc2 = mfma_16x16x32(st[u] < nsteps ? w[u] : zero4, x2[u], acc2);
+            }
         }
-        float (*slab)[64][4] = red[it & 1];
+        float (*slab)[64][4] = red[NBUF == 2 ? it & 1 : 0];
 #pragma unroll
         for (int r = 0; r < 4; ++r) slab[wave][lane][r] = acc[r];
+        if constexpr (W32) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) slab[NW + wave][lane][r] = acc2[r];
+        }
         __syncthreads();
         if (wave == it % NW) {
             float v[4];
@@ -309,10 +426,25 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
             }
             dg2_epilogue<MODE, ACT, OUTF32>(g, v, tile, lane, it == 0, resv);
         }
+        if constexpr (W32) {
+            if (wave == (it + 1) % NW) {
+                float v[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float s = 0.f;
+#pragma unroll
+                    for (int wv = 0; wv < NW; ++wv) s += slab[NW + wv][lane][r];
+                    v[r] = s;
+                }
+                const DecGemm2Args g2 = second_half();
+                dg2_epilogue<MODE, ACT, OUTF32>(g2, v, tile, lane, it == 0, resv2);
+            }
+            if (NBUF == 1) __syncthreads();           // one slab: the next tile's partial products wait for this tile's readers
+        }
     }
 }
 
-// sums of squares of the rows of x [M <= 16, K] (after the embedding gather): ss[r][0] = sum, ss[r][1 .. nss) = 0
+// sums of squares of the rows of x [M <= 32, K] (after the embedding gather): ss[r][0] = sum, ss[r][1 .. nss) = 0
 __global__ __launch_bounds__(256) void row_sumsq_kernel(const bf16_t* x, long ldx, int K, float* ss, int nss) {
     __shared__ float part[4];
     const int r = (int)blockIdx.x, tid = (int)threadIdx.x;
@@ -411,6 +543,8 @@ __global__ __launch_bounds__(256) void dec_pack_fp8_kernel(const bf16_t* W, long
 
 // waves per workgroup and 16-byte chunks per lane of a projection with `nsteps` k-steps (one rule for the launcher and for the fp8
 // packer, which must refuse what the fp8 kernel cannot stream)
+// (generation.rows32_form_exists in bioreason_amd/generation.py restates this rule and launch_dg2's 32-row refusals for the host's
+//  fallback to row chunks: change them together)
 static void dg2_waves_and_chunks(int nsteps, bool wide, int& nw, int& nl) {
     nw = (wide && nsteps >= 128) ? 16 : (nsteps >= 64 ? 8 : 4);
     const int spw = (nsteps + nw - 1) / nw;
@@ -435,8 +569,9 @@ static int launch_dg2(const DecGemm2Args& g, bra_stream_t st) {
     // (wide rows beyond one register round — Qwen3-4B's down projection, K = 9728 — take the generic multi-round loop like 8 rows;
     //  only the folded-norm form, refused above, is tied to the single-round path)
     // fast form: see the kernel; everything it assumes is checked here
-    const bool fits32 = g.ldx < (1 << 24) && g.ldres < (1 << 24) && 16 * g.ldx < (1L << 30) && 16 * g.ldres + g.N < (1L << 30) &&
-                        16L * g.nss_in < (1L << 24);
+    constexpr long ROWS = WIDE == 2 ? 32 : 16;
+    const bool fits32 = g.ldx < (1 << 24) && g.ldres < (1 << 24) && ROWS * g.ldx < (1L << 30) && ROWS * g.ldres + g.N < (1L << 30) &&
+                        ROWS * g.nss_in < (1L << 24);
 #ifdef BRA_DEBUG
     const bool probed = g.probe != nullptr;          // the fast form carries no stamps
 #else
@@ -454,14 +589,37 @@ static int launch_dg2(const DecGemm2Args& g, bra_stream_t st) {
             }                                                                                                                  \
         }                                                                                                                      \
         if (g.wscale) return BRA_ERR_UNSUPPORTED;                                                                              \
-        if constexpr (NORM != 1) {                                                                                             \
+        /* (32 rows, folded norm on 16 waves x 12 chunks — a hidden size of 6144: the statistics fold does not fit 128 registers) */ \
+        if constexpr (NORM != 1 && !(WIDE == 2 && NORM == 2 && NW_ == 16 && NL_ == 12)) {                                      \
             if (fast) {                                                                                                        \
                 BRA_LAUNCH((dec_gemm2_kernel<MODE, NORM, ACT, OUTF32, NW_, NL_, WIDE, 1, 1>), grid, dim3(NW_ * 64), 0, st, BRA_DG2_HEAD_ARGS(g), g); \
                 break;                                                                                                         \
             }                                                                                                                  \
         }                                                                                                                      \
-        if (g.packed & 1) BRA_LAUNCH((dec_gemm2_kernel<MODE, NORM, ACT, OUTF32, NW_, NL_, WIDE, 1>), grid, dim3(NW_ * 64), 0, st, BRA_DG2_HEAD_ARGS(g), g); \
-        else BRA_LAUNCH((dec_gemm2_kernel<MODE, NORM, ACT, OUTF32, NW_, NL_, WIDE, 0>), grid, dim3(NW_ * 64), 0, st, BRA_DG2_HEAD_ARGS(g), g);      \
+        if constexpr (WIDE == 2) {                                                                                             \
+            /* 32 rows outside the fast form: K beyond one register round runs the multi-round loop as its own kernel (WIDE == 3);  \
+               one clamped round only in the (waves, chunks) forms that hold both row halves without scratch — NW * NL <= 64 —     \
+               anything else is refused and the caller splits the batch */                                                          \
+            if (nsteps > NW_ * NL_) {                                                                                          \
+                /* (16 waves, 128 registers per lane: packed weights in 8 chunks — Qwen3-4B's down projection — and nothing else) */ \
+                if constexpr (NORM == 0 && (NW_ < 16 || NL_ == 8)) {                                                           \
+                    if (g.packed & 1) {                                                                                        \
+                        BRA_LAUNCH((dec_gemm2_kernel<MODE, NORM, ACT, OUTF32, NW_, NL_, 3, 1>), grid, dim3(NW_ * 64), 0, st, BRA_DG2_HEAD_ARGS(g), g); \
+                        break;                                                                                                 \
+                    }                                                                                                          \
+                    if constexpr (NW_ < 16) {                                                                                  \
+                        BRA_LAUNCH((dec_gemm2_kernel<MODE, NORM, ACT, OUTF32, NW_, NL_, 3, 0>), grid, dim3(NW_ * 64), 0, st, BRA_DG2_HEAD_ARGS(g), g); \
+                        break;                                                                                                 \
+                    }                                                                                                          \
+                }                                                                                                              \
+                return BRA_ERR_UNSUPPORTED;                                                                                    \
+            }                                                                                                                  \
+            if constexpr (NW_ * NL_ > 64) return BRA_ERR_UNSUPPORTED;                                                          \
+        }                                                                                                                      \
+        if constexpr (!(WIDE == 2 && NW_ * NL_ > 64)) {                                                                        \
+            if (g.packed & 1) BRA_LAUNCH((dec_gemm2_kernel<MODE, NORM, ACT, OUTF32, NW_, NL_, WIDE, 1>), grid, dim3(NW_ * 64), 0, st, BRA_DG2_HEAD_ARGS(g), g); \
+            else BRA_LAUNCH((dec_gemm2_kernel<MODE, NORM, ACT, OUTF32, NW_, NL_, WIDE, 0>), grid, dim3(NW_ * 64), 0, st, BRA_DG2_HEAD_ARGS(g), g);  \
+        }                                                                                                                      \
     } while (0)
     if (nw == 16) {
         if constexpr (WIDE != 0) { if (nl == 12) BRA_DG2(16, 12); else if (nl == 8) BRA_DG2(16, 8); else BRA_DG2(16, 4); }
@@ -522,7 +680,7 @@ static int dec_gemm2_any(const void* x, long ldx, const float* ss_in, int nss_in
                         const float* wscale) {
     (void)probe;
     if (wscale && (M > 8 || !(packed & 1) || (norm_w && !(packed & 2)))) return BRA_ERR_UNSUPPORTED;   // fp8 weights: <= 8 rows, packed, norm folded or absent
-    if (M <= 0 || M > 16 || N <= 0 || K <= 0 || K % 32 || ldx % 8 || ldw % 8 || !x || !W || !out) return BRA_ERR_ARG;
+    if (M <= 0 || M > 32 || N <= 0 || K <= 0 || K % 32 || ldx % 8 || ldw % 8 || !x || !W || !out) return BRA_ERR_ARG;
     if (act && (N % 16 || out_f32 || res || ss_out)) return BRA_ERR_ARG;
     if (out_f32 && res) return BRA_ERR_ARG;            // (out_f32 with ss_out: per-tile maxima of the logits, 16-column tiles)
     if (norm_w && (!ss_in || nss_in < 32 || nss_in % 32 || nss_in > 256)) return BRA_ERR_ARG;
@@ -537,6 +695,19 @@ static int dec_gemm2_any(const void* x, long ldx, const float* ss_in, int nss_in
     if (packed && (N % (diag ? 8 : 16) || K % (diag ? 64 : 32))) return BRA_ERR_ARG;
     bra_stream_t st = (bra_stream_t)stream;
     if ((packed & 2) && !(packed & 1)) return BRA_ERR_ARG;
+    if (M > 16) {
+        // 17 .. 32 rows: the 16-row form's tiles, weights (bra_dec_pack_weights_rows(rows = 16)) and statistics rule, two row halves
+        // per weight fragment
+        if (norm_w && !(packed & 2)) return BRA_ERR_UNSUPPORTED;
+        if (norm_w) {
+            if (act) return launch_dg2<0, 2, 1, 0, 2>(g, st);
+            if (out_f32) return launch_dg2<0, 2, 0, 1, 2>(g, st);
+            return launch_dg2<0, 2, 0, 0, 2>(g, st);
+        }
+        if (act) return launch_dg2<0, 0, 1, 0, 2>(g, st);
+        if (out_f32) return launch_dg2<0, 0, 0, 1, 2>(g, st);
+        return launch_dg2<0, 0, 0, 0, 2>(g, st);
+    }
     if (wide) {
         // statistics only in the folded form (rstd in the epilogue); the weights must be packed for 16-column tiles
         if (norm_w && !(packed & 2)) return BRA_ERR_UNSUPPORTED;
@@ -610,7 +781,7 @@ extern "C" int bra_dec_pack_weights_fp8(const void* W, long ldw, int N, int K, i
 }
 
 extern "C" int bra_row_sumsq(const void* x, long ldx, int M, int K, float* ss, int nss, void* stream) {
-    if (M <= 0 || M > 16 || K <= 0 || K % 8 || ldx % 8 || !x || !ss || nss < 1) return BRA_ERR_ARG;
+    if (M <= 0 || M > 32 || K <= 0 || K % 8 || ldx % 8 || !x || !ss || nss < 1) return BRA_ERR_ARG;
     BRA_LAUNCH(row_sumsq_kernel, dim3(M), dim3(256), 0, (bra_stream_t)stream, (const bf16_t*)x, ldx, K, ss, nss);
     return BRA_LAUNCH_STATUS();
 }

@@ -167,7 +167,8 @@ def rollout_weights(model, rows: int = 8):
     arena = model.arena
     pack = os.environ.get("BRA_DEC_PACK", "1") == "1"
     fold = pack and os.environ.get("BRA_DEC_FOLD", "1") == "1"
-    wide = rows > 8             # 9 .. 16 sequences: every projection is packed for 16-column tiles (ops.dec_pack_weights(rows=16))
+    wide = rows > 8             # 9 .. 32 sequences: every projection is packed for 16-column tiles (ops.dec_pack_weights(rows=16));
+    #                             the 32-row projections stream the same image — there is no second copy of the rollout weights
     fp8 = rollout_fp8_enabled(model) and pack and fold and not wide
     key = (model._packed_sig, model._lora_enabled, pack, fold, wide, fp8, None if arena is None or arena.params is None else (arena.step_count, arena.params._version))
     cached = getattr(eng, "_rollout", None)
@@ -435,20 +436,26 @@ def _set_proj(d, R, use_packed: bool):
 
 
 def _packed_ok(B: int, rw) -> bool:
-    """the streaming projections (bra_dec_gemm2) take up to 16 rows; above 8 they need the norm-folded packed weights"""
+    """the streaming projections (bra_dec_gemm2) take up to 32 rows; above 8 they need the norm-folded packed weights"""
     if not all("Wqkv_p" in R for R in rw):
         return False
-    return B <= 8 or (B <= 16 and all(R.get("folded") for R in rw))
+    return B <= 8 or (B <= MAX_DECODE_ROWS32 and all(R.get("folded") for R in rw))
+
+
+def _norm_stat_nss(eng) -> int:
+    """columns of the statistics workspace, or 0 where the second-generation projections do not apply"""
+    nblk = eng.H // 8 if (eng.H % 8 == 0 and (eng.H + 15) // 16 < 256 and eng.H // 8 <= 256) else (eng.H + 15) // 16
+    nss = (nblk + 31) // 32 * 32
+    return 0 if (nss > 256 or os.environ.get("BRA_DEC_GEMM_V1") == "1") else nss
 
 
 def _norm_stat_ws(eng, dev, rows: int = 8):
-    """zeroed workspace [2][8 | 16][nss] of RMSNorm partial sums of squares for the bra_dec_gemm2 projections (None, 0: the
+    """zeroed workspace [2][8 | 16 | 32][nss] of RMSNorm partial sums of squares for the bra_dec_gemm2 projections (None, 0: the
     hidden size has more column workgroups than the 256 partials a consumer folds -> first-generation kernels)"""
-    nblk = eng.H // 8 if (eng.H % 8 == 0 and (eng.H + 15) // 16 < 256 and eng.H // 8 <= 256) else (eng.H + 15) // 16
-    nss = (nblk + 31) // 32 * 32
-    if nss > 256 or os.environ.get("BRA_DEC_GEMM_V1") == "1":
+    nss = _norm_stat_nss(eng)
+    if nss == 0:
         return None, 0
-    return torch.zeros((2, 16 if rows > 8 else 8, nss), dtype=torch.float32, device=dev), nss
+    return torch.zeros((2, ops._stat_rows(rows), nss), dtype=torch.float32, device=dev), nss
 
 
 def _uniform_groups(prompt_alias):
@@ -488,11 +495,51 @@ def decode_step(model, tok: torch.Tensor, cache: KVCache, kmask: torch.Tensor, p
     return ops.rmsnorm_fwd(x, eng.norm_w, eng.eps)
 
 
-MAX_DECODE_ROWS = 16            # sequences per launch of the streaming decode kernels (bra_dec_gemm2: one 16-row MFMA tile)
+MAX_DECODE_ROWS = 16            # sequences per launch of the 16-row streaming decode kernels (bra_dec_gemm2: one 16-row MFMA tile)
+MAX_DECODE_ROWS32 = 32          # ... of their 32-row form (two MFMAs per weight fragment): one token loop for 17 .. 32 sequences
 
 
-def _row_chunks(B: int, prompt_alias):
-    """[lo, hi) row ranges of at most MAX_DECODE_ROWS rows: consecutive whole prompt groups (rows with the same alias) where they
+def decode_rows_limit() -> int:
+    """sequences one token loop takes: 16 — batches above 16 rows run as 16-row chunks, each with its own prefill, cache and loop —
+    or, with BRA_DEC_ROWS32=1, 32 (one loop on the 32-row projections).  The one-loop path stays opt-in until it is measured against
+    the previous commit on one box (NOTES.md, "32 rows per weight stream")"""
+    return MAX_DECODE_ROWS32 if os.environ.get("BRA_DEC_ROWS32", "0") == "1" else MAX_DECODE_ROWS
+
+
+def rows32_form_exists(K: int, normed: bool, packed: bool = True) -> bool:
+    """launch_dg2's rule (k_decgemm.hip) for 17 .. 32 rows over 16-column tiles of 32 k: does a 32-row kernel exist for this K?
+    The fast form (packed weights, K exactly one register round of the (waves, chunks) the launcher picks) always, except the
+    folded norm on 16 waves x 12 chunks; one clamped round outside the fast form up to waves x chunks = 64; K beyond one round
+    without norm only — packed on 16 waves x 8 chunks or on fewer waves, plain layout on fewer than 16 waves."""
+    if K <= 0 or K % 32:
+        return False
+    nsteps = K // 32
+    nw = 16 if nsteps >= 128 else (8 if nsteps >= 64 else 4)
+    spw = (nsteps + nw - 1) // nw
+    nl = 12 if (spw >= 12 and spw % 12 == 0) else (10 if (spw == 10 and nw == 8) else (8 if spw > 4 else 4))
+    if nsteps > nw * nl:
+        return (not normed) and ((nw < 16) or (nl == 8 and packed))
+    if packed and nsteps == nw * nl and not (normed and nw == 16 and nl == 12):
+        return True
+    return nw * nl <= 64
+
+
+def _one_loop_ok(model, B: int) -> bool:
+    """17 .. 32 rows in ONE token loop: what the 32-row projections need is folded, bf16, fragment-packed rollout weights and the
+    second-generation statistics workspace; anything else (BRA_DEC_PACK / BRA_DEC_FOLD = 0, BRA_DEC_GEMM_V1, a shape the packer
+    refuses, fp8 rollout weights) keeps the 16-row chunks"""
+    eng = model.ensure_packed()
+    if _norm_stat_nss(eng) == 0 or rollout_fp8_enabled(model):      # (fp8 images stream against <= 8 rows: chunks, as before)
+        return False
+    # the K of every projection must select a 32-row form the library has (bra_dec_gemm2 returns BRA_ERR_UNSUPPORTED otherwise, and
+    # only at launch time): normed inputs (hidden size: qkv, gate/up, lm_head) and plain ones (q width: o; intermediate size: down)
+    if not (rows32_form_exists(eng.H, normed=True) and rows32_form_exists(eng.Nq, normed=False) and rows32_form_exists(eng.F, normed=False)):
+        return False
+    return _packed_ok(B, rollout_weights(model, rows=B))         # (the same wide image a 9 .. 16-row loop builds and caches)
+
+
+def _row_chunks(B: int, prompt_alias, max_rows: int = MAX_DECODE_ROWS):
+    """[lo, hi) row ranges of at most `max_rows` rows: consecutive whole prompt groups (rows with the same alias) where they
     fit, a larger group in pieces"""
     if prompt_alias is None:
         runs = [(i, i + 1) for i in range(B)]
@@ -505,13 +552,13 @@ def _row_chunks(B: int, prompt_alias):
                 lo = i
     chunks, cur = [], None
     for lo, hi in runs:
-        while hi - lo > MAX_DECODE_ROWS:                       # a group of more than 16 copies: pieces of 16
+        while hi - lo > max_rows:                              # a group of more than max_rows copies: pieces of max_rows
             if cur is not None:
                 chunks.append(cur)
                 cur = None
-            chunks.append((lo, lo + MAX_DECODE_ROWS))
-            lo += MAX_DECODE_ROWS
-        if cur is not None and hi - cur[0] <= MAX_DECODE_ROWS:
+            chunks.append((lo, lo + max_rows))
+            lo += max_rows
+        if cur is not None and hi - cur[0] <= max_rows:
             cur = (cur[0], hi)
         else:
             if cur is not None:
@@ -522,7 +569,7 @@ def _row_chunks(B: int, prompt_alias):
     return chunks
 
 
-def _generate_in_row_chunks(model, inputs_embeds, attention_mask, prompt_alias, force_tokens, eos_schedule, seed, kw):
+def _generate_in_row_chunks(model, inputs_embeds, attention_mask, prompt_alias, force_tokens, eos_schedule, seed, kw, max_rows=MAX_DECODE_ROWS):
     """`kw`: EVERY other keyword of generate() (built from its locals, so a keyword added later is forwarded too)"""
     B = inputs_embeds.shape[0]
     trace = kw.pop("trace_logits", None)
@@ -531,7 +578,7 @@ def _generate_in_row_chunks(model, inputs_embeds, attention_mask, prompt_alias, 
     eos0 = (list(eos_)[0] if len(eos_) else None) if isinstance(eos_, (list, tuple)) else eos_
     pad = int(kw["pad_token_id"]) if kw["pad_token_id"] is not None else (int(eos0) if eos0 is not None else 0)
     outs = []
-    for ci, (lo, hi) in enumerate(_row_chunks(B, prompt_alias)):
+    for ci, (lo, hi) in enumerate(_row_chunks(B, prompt_alias, max_rows)):
         alias = None
         if prompt_alias is not None:
             al = [int(a) for a in prompt_alias[lo:hi]]
@@ -578,13 +625,18 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
     eng = model.ensure_packed()
     B, P, H = inputs_embeds.shape
     dev = inputs_embeds.device
-    if B > MAX_DECODE_ROWS and native_step and decode_impl == "fused":
-        # the streaming decode kernels take up to 16 sequences per launch (one MFMA tile of rows); the reference's
-        # per_device_train_batch_size is free (grpo_config.py), so larger batches run as consecutive row chunks — whole prompt
-        # groups where they fit — each with its own prefill, cache and token loop
+    max_rows = MAX_DECODE_ROWS
+    if B > MAX_DECODE_ROWS and native_step and decode_impl == "fused" and decode_rows_limit() > MAX_DECODE_ROWS \
+            and _one_loop_ok(model, min(B, MAX_DECODE_ROWS32)):
+        max_rows = MAX_DECODE_ROWS32        # 17 .. 32 sequences: ONE prefill and ONE token loop on the 32-row projections
+    if B > max_rows and native_step and decode_impl == "fused":
+        # the streaming decode kernels take up to 32 sequences per launch (two MFMA tiles of rows per weight fragment; 16 with
+        # BRA_DEC_ROWS32=0 or without folded packed weights); the reference's per_device_train_batch_size is free
+        # (grpo_config.py), so larger batches run as consecutive row chunks — whole prompt groups where they fit — each with its
+        # own prefill, cache and token loop
         own = ("model", "inputs_embeds", "attention_mask", "prompt_alias", "force_tokens", "eos_schedule", "seed", "eng", "B", "P", "H", "dev")
         return _generate_in_row_chunks(model, inputs_embeds, attention_mask, prompt_alias, force_tokens, eos_schedule, seed,
-                                       {k: v for k, v in _call_kw.items() if k not in own})
+                                       {k: v for k, v in _call_kw.items() if k not in own}, max_rows)
     import time as _time
     _t0 = [_time.perf_counter()]
 
@@ -686,7 +738,7 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
         ops.tile_max(logits, tmax)
         sample_ws = torch.empty((2 * B * 8 * kk,), dtype=torch.float32, device=dev)
     fuse_embed = (dstate is not None and dstate.ss_ws is not None and force_tokens is None and sample_ws is not None
-                  and B <= 16 and (not do_sample or 1 <= top_k <= 64))     # (top_k = 0 / > 64: the general sampler, no fused gather)
+                  and B <= MAX_DECODE_ROWS32 and (not do_sample or 1 <= top_k <= 64))     # (top_k = 0 / > 64: the general sampler, no fused gather)
     rope_args = None
     if shared is not None and getattr(shared, "rope_rows", None) is not None:
         rope_args = (shared.cosT, shared.sinT, eng.hd, shared.rope_rows)

@@ -537,7 +537,7 @@ def colsum(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
 # --------------------------------------------------------------------------- GRPO / optimiser
 def sample(logits, temperature, top_k, top_p, do_sample, seed, step_t, finished, pad_id, out_ids, out_logp=None,
            eos_id=-1, tokens_out=None, ws=None, embed=None, eos_id2=-1):
-    """`embed` = (E [V, H], x [B, H], ss [8, nss] or None): the drawing wave also writes x[b] = E[token] and the RMSNorm
+    """`embed` = (E [V, H], x [B, H], ss [8 | 16 | 32, nss] or None): the drawing wave also writes x[b] = E[token] and the RMSNorm
     statistic of that row (two-stage path only: V >= 4096)."""
     B, V = logits.shape
     if do_sample and not (1 <= top_k <= 64):
@@ -628,9 +628,15 @@ def rope_rows(cosT: torch.Tensor, sinT: torch.Tensor, pos: torch.Tensor, hd: int
     get_lib().call("bra_rope_rows", cosT, sinT, pos, pos.numel(), hd, rows, current_stream(pos))
 
 
+def _stat_rows(M: int) -> int:
+    """rows of the statistics arrays the streaming projections fold for M batch rows"""
+    return 8 if M <= 8 else (16 if M <= 16 else 32)
+
+
 def row_sumsq(x: torch.Tensor, nss: int = 32) -> torch.Tensor:
-    """partial sums of squares of the rows of x [M<=16, K] in the layout bra_dec_gemm2 consumes: fp32 [8, nss] ([16, nss] for M > 8)"""
-    ss = torch.zeros((16 if x.shape[0] > 8 else 8, nss), dtype=torch.float32, device=x.device)
+    """partial sums of squares of the rows of x [M<=32, K] in the layout bra_dec_gemm2 consumes: fp32 [8, nss] ([16, nss] for M > 8,
+    [32, nss] for M > 16)"""
+    ss = torch.zeros((_stat_rows(x.shape[0]), nss), dtype=torch.float32, device=x.device)
     get_lib().call("bra_row_sumsq", x, _ld(x), x.shape[0], x.shape[1], ss, nss, current_stream(x))
     return ss
 
@@ -644,7 +650,7 @@ def dec_gemm2(x, W, ss_in=None, norm_w=None, eps=1e-6, res=None, act=False, out_
     N = W.shape[0]
     out = torch.empty((M, N // 2 if act else N), dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
     nss_out = (N // 8 + 32) // 32 * 32
-    ss_out = torch.zeros((16 if M > 8 else 8, nss_out), dtype=torch.float32, device=x.device) if want_ss else None
+    ss_out = torch.zeros((_stat_rows(M), nss_out), dtype=torch.float32, device=x.device) if want_ss else None
     if tile_max is not None:
         assert out_f32 and not want_ss
         ss_out, nss_out, want_ss = tile_max, _ld(tile_max), True

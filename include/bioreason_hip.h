@@ -256,9 +256,15 @@ int bra_gemm_fp8_nt(const void* A8, long lda, const float* sa, const void* B8, l
  * norm weights or statistics ahead of the MFMAs (TF:qwen3:59-64 rounds the normalised activation to bf16 instead: the two
  * differ by bf16 rounding placement only; rollout path). */
 int bra_dec_pack_weights(const void* W, long ldw, int N, int K, int act, int out_f32, const void* norm_w, void* out, void* stream);
-/* the same for a given number of batch rows: bra_dec_gemm2 takes up to 16 rows (two prompts x 8 rollouts per GPU); above 8 rows
- * every projection streams 16-column tiles (the 8-column "diagonal" tiles of the N = hidden projections hold 8 rows), the
- * RMSNorm must be folded (packed = 3) and the statistics arrays have 16 rows */
+/* the same for a given number of batch rows (1 .. 16): bra_dec_gemm2 / bra_dec_gemm2_packed / bra_row_sumsq take up to 32 rows.
+ * Above 8 rows every projection streams 16-column tiles (the 8-column "diagonal" tiles of the N = hidden projections hold 8
+ * rows), the RMSNorm must be folded (packed = 3) and the statistics arrays have 16 rows.  17 .. 32 rows (three or four prompts
+ * x 8 rollouts per GPU) stream the SAME rows = 16 image — each weight fragment is requested once and multiplied against both
+ * 16-row halves of the batch — with 32-row statistics arrays (`ss_ws` of the step functions: float [2][32][nss]); row r of
+ * such a call is bit-identical to the same row computed by a 9 .. 16-row call.  BRA_ERR_UNSUPPORTED above 16 rows for an
+ * unfolded norm, for fp8 images (bra_dec_gemm2_fp8) and, outside the fast form (packed, K exactly one register round), for the
+ * (waves, chunks) forms that cannot hold both row halves in registers — one clamped round above waves x chunks = 64, K beyond
+ * one round on 16 waves unless packed in 8 chunks, the folded norm at K = 6144: the caller splits the batch. */
 int bra_dec_pack_weights_rows(const void* W, long ldw, int N, int K, int act, int out_f32, const void* norm_w, int rows, void* out,
                               void* stream);
 int bra_row_sumsq(const void* x, long ldx, int M, int K, float* ss, int nss, void* stream);
