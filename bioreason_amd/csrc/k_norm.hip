@@ -96,7 +96,15 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const bf16_t* x, lon
 #pragma unroll
         for (int i = 0; i < 8; ++i) s += f[i];
     }
-    const float mean = wave_sum<64>(s) / (float)cols;
+    const float tot = wave_sum<64>(s);
+    float mean = tot / (float)cols;
+    {
+        // one correction step.  Under -ffast-math the division is a reciprocal and a product, an ulp off for most widths (a sum of 504
+        // equal values never gives the value back), and at eps = 1e-12 that ulp is what a constant row is then normalised by: y = b +- 0.2 w
+        // where the reference gives b.  The residual is exact in one fma; it must not be folded back into tot - tot
+#pragma clang fp reassociate(off)
+        mean += __builtin_fmaf(-mean, (float)cols, tot) / (float)cols;
+    }
     float v = 0.f;
     for (int c = lane * 8; c < cols; c += 512) {
         float f[8];

@@ -9,6 +9,11 @@ against a float64 reference and its own rounding bound, at adversarial values, s
 The loss path (lmhead_logprob, grpo_loss, lmhead_dlogits, gemm_nt with E^T) and group_advantage / eos_mask likewise: the bounds
 here are the coarse check; tests/test_loss_path_rowwise.py holds every row (every element, on exact logits) against float64, with
 targets placed on the chunk, fragment and ragged-tail columns of the epilogues, on every GEMM kernel the dispatch can take.
+The norms (rmsnorm_fwd / bwd, layernorm_fwd), SwiGLU, QK-norm + RoPE and the movers (head_transpose, transpose2d, group_sum,
+group_broadcast, gather / scatter_rows, embed_scatter) likewise: the bounds here are the coarse check; tests/test_layer_glue_rowwise.py
+holds every element — the forward kernels bit for bit against a float64 twin with the kernels' rounding points, the backward
+kernels against float64 autograd under a first-order bound, the movers bit for bit with sentinels around every destination — at
+every wave pattern, tile edge and pitch, on both RoPE kernel families, with eps, overflow and cancellation in play.
 """
 import math
 
