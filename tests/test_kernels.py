@@ -14,6 +14,11 @@ group_broadcast, gather / scatter_rows, embed_scatter) likewise: the bounds here
 holds every element — the forward kernels bit for bit against a float64 twin with the kernels' rounding points, the backward
 kernels against float64 autograd under a first-order bound, the movers bit for bit with sentinels around every destination — at
 every wave pattern, tile edge and pitch, on both RoPE kernel families, with eps, overflow and cancellation in play.
+The GEMM family (gemm_nt on every kernel body, the skinny kernel, split-K, the SwiGLU epilogue, gemm_fp8_nt), wgrad_tn and the masked
+LoRA kernels likewise: one Frobenius ratio per tensor here is the coarse check; tests/test_gemm_family_rowwise.py holds every element —
+bit for bit against float64 on integer operands whose partial sums are exact fp32 numbers in any order, under a first-order bound on
+random ones — with sentinels around every output, at the tile edges, ragged quads, K-tile counts, slices and chunks of each kernel, and
+on every route the product library's dispatch can take.
 """
 import math
 

@@ -123,10 +123,10 @@ def _record(name, ratios, dev):
 
 
 # ----------------------------------------------------------------------------- dispatch mirror
-def _pick_variant(M, N, K, forced=-1):
+def _pick_variant(M, N, K, forced=-1, K2=0):
     if forced >= 0:
         return 6 if forced >= 6 else forced
-    if K % 64 == 0:
+    if K % 64 == 0 and K2 % 64 == 0:
         t = -(-M // 256) * -(-N // 256)
         rounds = -(-t // 256)
         if t >= 140 and (t <= 256 or 100 * t >= 60 * rounds * 256):
@@ -158,6 +158,67 @@ def _kernel(M, N, K, forced=-1):
     if K % 64 == 0 and v >= 4:
         return f"glds{_glds_rows(M, N, forced)}"
     return "nt256" if v in (2, 3) else "nt128"
+
+
+# bra_gemm_bf16_nt (tests/test_gemm_family_rowwise.py): the same functions plus the second operand pair, the skinny kernel, pick_w4 and
+# ring_split_rows.  No knob: the product library's choice is a pure function of (M, N, K, K2).
+W4_TILES = {1: (160, 256), 2: (128, 256), 3: (160, 128), 4: (128, 128)}
+
+
+def _pick_w4(M, N, K, K2=0):
+    """pick_w4: the four-wave configuration (1..4) when it is the argmin of the launch-time model, else 0"""
+    if K % 64 or K2 % 64 or M < 128 or N < 128 or K + K2 < 256:
+        return 0
+    if -(-M // 256) * -(-N // 256) > 256:
+        return 0
+    cands = ((256, 256, 5.9, 0), (256, 128, 4.27, 0), (192, 128, 4.56, 0), (128, 128, 3.75, 0),
+             (160, 256, 4.5, 1), (128, 256, 4.5, 2), (160, 128, 4.5, 3), (128, 128, 4.5, 4))
+    kk = 2.0e-6 * float(K + K2)
+    best, best_t = 0, 1e30
+    for bm, bn, rate, w4 in cands:
+        tiles = -(-M // bm) * -(-N // bn)
+        t = float(-(-tiles // 256)) * (kk * bm * bn / rate + 3.5)
+        if t < best_t:
+            best_t, best = t, w4
+    return best
+
+
+def _ring_split_rows(M, N, K, K2=0):
+    """ring_split_rows: rows of the ring part when the last round of 256 x 256 tiles is less than half full, else 0"""
+    if K % 64 or K2 % 64 or _pick_variant(M, N, K, K2=K2) != 6 or _pick_w4(M, N, K, K2):
+        return 0
+    tm, tn = -(-M // 256), -(-N // 256)
+    t = tm * tn
+    R = t // 256
+    rem = t - R * 256
+    if R < 1 or rem == 0 or 2 * rem >= 256:
+        return 0
+    rm = (R * 256) // tn
+    if rm <= 0 or rm >= tm:
+        return 0
+    halves = -(-(M - rm * 256) // 256) * -(-N // 128)
+    if halves < 32 or N * (K + K2) < 6 * 1024 * 1024:
+        return 0
+    return rm * 256 if R + 0.55 * -(-halves // 256) < (R + 1) - 0.15 else 0
+
+
+def _route_bf16(M, N, K, K2=0):
+    """the kernel(s) bra_gemm_bf16_nt launches in the product library: skinny | split (ring + LDS-DMA 256 rows) | w4-1..4 | ring |
+    glds256 / 192 / 128 | nt128 (K % 64 != 0: its BK = 32 instance)"""
+    if M <= 16:
+        return "skinny"
+    if _ring_split_rows(M, N, K, K2) > 0:
+        return "split"
+    if K % 64 == 0 and K2 % 64 == 0:
+        w4 = _pick_w4(M, N, K, K2)
+        if w4:
+            return f"w4-{w4}"
+        v = _pick_variant(M, N, K, K2=K2)
+        if v == 6:
+            return "ring"
+        if v >= 4:
+            return f"glds{_glds_rows(M, N)}"
+    return "nt128"
 
 
 FAMILY = {"nt128": "register-staged", "nt256": "register-staged", "ring": "ring", "glds256": "LDS-DMA", "glds192": "LDS-DMA", "glds128": "LDS-DMA"}
