@@ -22,6 +22,12 @@ struct DecGemm2Args {
     float inv_K;                        // 1 / K rounded on the host (NORM == 2: mean of squares = fma(sum, inv_K, eps))
 };
 
+// The 8-column (diagonal) tile rule, host side: an N-wide projection of <= 8 rows takes 8-column tiles where 16-column tiles would leave
+// CUs idle — as long as the N / 8 statistics partials they emit still fit the 256 a consumer folds (N = 2560, Qwen3-4B: 16-column
+// tiles, 160 workgroups).  The projection, both packers and the step driver ask here; what else a caller needs (K % 64 == 0, no
+// SwiGLU / fp32 epilogue, <= 8 rows) it adds itself.  bra_dec_stat_cols exports the statistics columns that follow from it.
+inline bool dg2_diag_tiles(int N) { return N % 8 == 0 && (N + 15) / 16 < 256 && N / 8 <= 256; }
+
 // 100 MHz wall clock (s_memrealtime); compiled in only under BRA_DEBUG (one uniform branch per stamp when unused)
 #if defined(BRA_EMU) || !defined(BRA_DEBUG)
 __device__ __forceinline__ void dg2_stamp(const DecGemm2Args&, int) {}

@@ -543,14 +543,28 @@ __global__ __launch_bounds__(256) void dec_pack_fp8_kernel(const bf16_t* W, long
 
 // waves per workgroup and 16-byte chunks per lane of a projection with `nsteps` k-steps (one rule for the launcher and for the fp8
 // packer, which must refuse what the fp8 kernel cannot stream)
-// (generation.rows32_form_exists in bioreason_amd/generation.py restates this rule and launch_dg2's 32-row refusals for the host's
-//  fallback to row chunks: change them together)
 static void dg2_waves_and_chunks(int nsteps, bool wide, int& nw, int& nl) {
     nw = (wide && nsteps >= 128) ? 16 : (nsteps >= 64 ? 8 : 4);
     const int spw = (nsteps + nw - 1) / nw;
     // (10: K = 2560, Qwen3-4B's hidden size — instantiated for the 8-wave form only; 4- and 16-wave shapes with ten steps per wave
     //  take nl = 8 in the generic multi-round loop, as before that form existed)
     nl = (spw >= 12 && spw % 12 == 0) ? 12 : ((spw == 10 && nw == 8) ? 10 : (spw > 4 ? 8 : 4));
+}
+
+// 17 .. 32 rows over 16-column tiles of 32 k: is there a 32-row kernel for this K?  (launch_dg2<.., WIDE = 2> asks before it
+// dispatches; bra_dec_gemm2_rows32_ok exports the answer to the host, which keeps 16-row chunks where it is no.)
+// The fast form (packed weights, K exactly one register round of the (waves, chunks) above) always, except the folded norm on
+// 16 waves x 12 chunks — a hidden size of 6144: the statistics fold does not fit 128 registers; one clamped round outside the fast
+// form only where both row halves are held without scratch, waves x chunks <= 64; K beyond one round without norm only — packed on
+// 16 waves x 8 chunks (Qwen3-4B's down projection) or on fewer waves, plain layout on fewer than 16 waves.
+static bool dg2_rows32_ok(int K, bool normed, bool packed) {
+    if (K <= 0 || K % 32) return false;
+    const int nsteps = K / 32;
+    int nw, nl;
+    dg2_waves_and_chunks(nsteps, true, nw, nl);
+    if (nsteps > nw * nl) return !normed && (nw < 16 || (nl == 8 && packed));
+    if (packed && nsteps == nw * nl && !(normed && nw == 16 && nl == 12)) return true;
+    return nw * nl <= 64;
 }
 
 template <int MODE, int NORM, int ACT, int OUTF32, int WIDE = 0>
@@ -562,6 +576,7 @@ static int launch_dg2(const DecGemm2Args& g, bra_stream_t st) {
     int nw, nl;
     dg2_waves_and_chunks(nsteps, WIDE != 0, nw, nl);
     if (NORM == 2 && (nsteps + nw * nl - 1) / (nw * nl) != 1) return BRA_ERR_UNSUPPORTED;     // folded norm: single-round path only
+    if (WIDE == 2 && !dg2_rows32_ok(g.K, NORM == 2, (g.packed & 1) != 0)) return BRA_ERR_UNSUPPORTED;
     const int ntiles = MODE ? g.N / 8 : (g.N + 15) / 16;
     // one workgroup of 8 waves (two of 4) per CU, looping over the tiles; the 16-wave form takes one tile per workgroup
     const int gmax = nw == 16 ? ntiles : (nw >= 8 ? 256 : 512);
@@ -686,9 +701,8 @@ static int dec_gemm2_any(const void* x, long ldx, const float* ss_in, int nss_in
     if (norm_w && (!ss_in || nss_in < 32 || nss_in % 32 || nss_in > 256)) return BRA_ERR_ARG;
     if (res && ldres % 4) return BRA_ERR_ARG;
     const bool wide = M > 8;                     // 9 .. 16 rows: 16-column tiles everywhere (a diagonal tile holds 8 rows)
-    // 8-column (diagonal) tiles where 16-column tiles would leave CUs idle — as long as the N / 8 statistics partials they emit still
-    // fit the 256 a consumer folds (N = 2560, Qwen3-4B: 16-column tiles, 160 workgroups)
-    const bool diag = !wide && !act && !out_f32 && N % 8 == 0 && K % 64 == 0 && (N + 15) / 16 < 256 && N / 8 <= 256;
+    // 8-column (diagonal) tiles: dg2_diag_tiles (bra_decgemm.h)
+    const bool diag = !wide && !act && !out_f32 && K % 64 == 0 && dg2_diag_tiles(N);
     if (ss_out && nss_out < (diag ? N / 8 : (N + 15) / 16)) return BRA_ERR_ARG;
     DecGemm2Args g = {(const bf16_t*)x, ldx, ss_in, nss_in, (const bf16_t*)norm_w, eps, (const bf16_t*)W, ldw,
                       (const bf16_t*)res, ldres, out, ldo, ss_out, nss_out, M, N, K, packed, wscale, BRA_DBG_INIT((unsigned long long*)probe) 1.f / (float)K};
@@ -746,7 +760,7 @@ extern "C" int bra_dec_pack_weights(const void* W, long ldw, int N, int K, int a
 extern "C" int bra_dec_pack_weights_rows(const void* W, long ldw, int N, int K, int act, int out_f32, const void* norm_w, int rows,
                                          void* out, void* stream) {
     if (!W || !out || N <= 0 || K <= 0 || ldw % 8 || rows <= 0 || rows > 16) return BRA_ERR_ARG;
-    const bool diag = rows <= 8 && !act && !out_f32 && N % 8 == 0 && K % 64 == 0 && (N + 15) / 16 < 256 && N / 8 <= 256;      // bra_dec_gemm2's rule
+    const bool diag = rows <= 8 && !act && !out_f32 && K % 64 == 0 && dg2_diag_tiles(N);      // bra_dec_gemm2's rule
     if (N % (diag ? 8 : 16) || K % (diag ? 64 : 32)) return BRA_ERR_UNSUPPORTED;
     const long nchunk = (long)N * K / 8;
     const dim3 grid((unsigned)((nchunk + 255) / 256));
@@ -761,7 +775,7 @@ extern "C" int bra_dec_pack_weights_rows(const void* W, long ldw, int N, int K, 
 extern "C" int bra_dec_pack_weights_fp8(const void* W, long ldw, int N, int K, int act, int out_f32, const void* norm_w, void* out_q,
                                         float* out_scale, void* stream) {
     if (!W || !out_q || !out_scale || N <= 0 || K <= 0 || ldw % 8) return BRA_ERR_ARG;
-    const bool diag = !act && !out_f32 && N % 8 == 0 && K % 64 == 0 && (N + 15) / 16 < 256 && N / 8 <= 256;      // bra_dec_gemm2's rule
+    const bool diag = !act && !out_f32 && K % 64 == 0 && dg2_diag_tiles(N);      // bra_dec_gemm2's rule
     if (N % (diag ? 8 : 16) || K % (diag ? 128 : 64)) return BRA_ERR_UNSUPPORTED;
     {   // only what bra_dec_gemm2_fp8 streams: K exactly one register round of the (waves, chunks) the launcher picks
         int nw, nl;
@@ -779,6 +793,16 @@ extern "C" int bra_dec_pack_weights_fp8(const void* W, long ldw, int N, int K, i
     else BRA_LAUNCH((dec_pack_fp8_kernel<0>), grid, dim3(256), 0, st, (const bf16_t*)W, ldw, N, K, (const bf16_t*)norm_w, out_scale, (unsigned*)out_q);
     return BRA_LAUNCH_STATUS();
 }
+
+// statistics columns of a step whose hidden size is H: the workgroups of an N = H projection (one partial each), as a multiple of 32;
+// 0 where that is more than the 256 a consumer folds (the step then runs the first-generation projections)
+extern "C" int bra_dec_stat_cols(int H) {
+    if (H <= 0) return 0;
+    const int nss = ((dg2_diag_tiles(H) ? H / 8 : (H + 15) / 16) + 31) / 32 * 32;
+    return nss > 256 ? 0 : nss;
+}
+
+extern "C" int bra_dec_gemm2_rows32_ok(int K, int normed, int packed) { return dg2_rows32_ok(K, normed != 0, packed != 0) ? 1 : 0; }
 
 extern "C" int bra_row_sumsq(const void* x, long ldx, int M, int K, float* ss, int nss, void* stream) {
     if (M <= 0 || M > 32 || K <= 0 || K % 8 || ldx % 8 || !x || !ss || nss < 1) return BRA_ERR_ARG;

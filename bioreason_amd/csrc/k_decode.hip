@@ -4,6 +4,7 @@
 // the step is one C-ABI call that enqueues every kernel on the caller's stream.  No device code here.
 #include "bra_device.h"
 #include "bra_api_internal.h"
+#include "bra_decgemm.h"
 #include "../../include/bioreason_hip.h"
 #ifdef BRA_DEBUG
 #include "../../include/bioreason_hip_debug.h"
@@ -83,7 +84,7 @@ struct StepGemms {
 };
 static StepGemms step_gemms(float* ss_ws, int nss, int B, int H, int Nq, int Nqkv, int F, int V, float eps, void* stream) {
     StepGemms s;
-    const int nblk = (H % 8 == 0 && (H + 15) / 16 < 256 && H / 8 <= 256) ? H / 8 : (H + 15) / 16;      // workgroups of an N = H projection (bra_dec_gemm2's tile rule)
+    const int nblk = bra::dg2_diag_tiles(H) ? H / 8 : (H + 15) / 16;      // workgroups of an N = H projection (bra_dec_gemm2's tile rule)
     s.v2 = ss_ws && B <= 32 && nss >= 32 && nss % 32 == 0 && nss <= 256 && nss >= nblk;
     // two statistics arrays [rows][nss], rows = 8, (9 .. 16 sequences) 16 or (17 .. 32 sequences: the 32-row projections) 32
     s.ssx = ss_ws; s.ssh = ss_ws ? ss_ws + (B > 16 ? 32 : (B > 8 ? 16 : 8)) * (long)nss : nullptr; s.nss = nss;
@@ -135,6 +136,46 @@ static int sg_head(const StepGemms& s, const void* x, const void* norm_w, const 
     return bra_tile_max(logits, s.V, s.B, s.V, tmax, nt, s.stream);
 }
 
+// What the fused step entry points below share: the projections' plan, the arguments of the prologue and of the head, the row
+// buffers, and the "record 0 only" fields of the layer table read once (null / 0 for an empty table).
+struct StepCtx {
+    const Layer* ls; int L; StepGemms sg;
+    const void *E, *norm_w; const int* tok; int embed_done; void *x, *qkv, *o, *h, *act; float* logits;
+    const void* head_packed; int head_folded; const float* sc_head; float* head_tmax; const float* rope_rows;
+};
+static StepCtx step_ctx(const void* layers_host, int L, int B, int H, int Hq, int Hkv, int hd, int F, int V, float eps, const void* E,
+                        const void* norm_w, const int* tok, int embed_done, void* x, void* qkv, void* o, void* h, void* act, float* ss_ws,
+                        int nss, float* logits, void* stream) {
+    const Layer* ls = (const Layer*)layers_host;
+    const Layer none = {}, &r0 = L > 0 ? ls[0] : none;
+    return {ls, L, step_gemms(ss_ws, nss, B, H, Hq * hd, (Hq + 2 * Hkv) * hd, F, V, eps, stream), E, norm_w, tok, embed_done, x, qkv, o, h, act,
+            logits, r0.head_packed, r0.flags & 4, (r0.flags & 16) ? r0.sc_head : nullptr, r0.head_tmax, r0.rope_rows};
+}
+// x = E[tok] and its RMSNorm statistics, unless bra_sample_embed already left both
+static int step_begin(const StepCtx& c) {
+    if (c.embed_done && c.sg.v2) return 0;
+    const int rc = bra_embed_scatter_fwd(c.tok, nullptr, c.E, c.sg.H, nullptr, 0, c.x, c.sg.H, c.sg.B, c.sg.H, c.sg.stream);
+    return rc ? rc : sg_begin(c.sg, c.x);
+}
+// final RMSNorm + tied lm_head into fp32 logits [B, V] when `logits` is non-null
+static int step_head(const StepCtx& c) {
+    return c.logits ? sg_head(c.sg, c.x, c.norm_w, c.E, c.head_packed, c.head_folded, c.logits, c.head_tmax, c.sc_head) : 0;
+}
+// One step: prologue; per layer the qkv projection, attn(layer) (q / k norm + RoPE, cache append, attention into `o`) and the o /
+// gate-up / down projections; head.  The entry points differ in `attn` only.
+template <class Attn>
+static int run_step(const StepCtx& c, Attn&& attn) {
+    int rc;
+    if ((rc = step_begin(c))) return rc;
+    for (int li = 0; li < c.L; ++li) {
+        const Layer& l = c.ls[li];
+        if ((rc = sg_qkv(c.sg, l, c.x, c.qkv))) return rc;
+        if ((rc = attn(l))) return rc;
+        if ((rc = sg_tail(c.sg, l, c.o, c.x, c.h, c.act))) return rc;
+    }
+    return step_head(c);
+}
+
 // Fused variant (k_decfused.hip): 6 launches per layer.  The layer records carry ROLLOUT weights in
 // Wqkv / Wo / Wgu / Wd: LoRA already merged (W + s B A, the same merge PEFT's merge_and_unload performs,
 // reason.py:428-446) and gate/up rows interleaved in blocks of 8 for the SwiGLU epilogue; the LoRA fields are unused.
@@ -144,29 +185,14 @@ extern "C" int bra_qwen_decode_step_fused(const void* layers_host, int L, int B,
                                           const float* cosT, const float* sinT, const int* tok, const int* pos,
                                           const void* kmask, int cur_len, const int* len_dev, int embed_done, void* x, void* qkv, void* o, void* h, void* act,
                                           float* ss_ws, int nss, float* part_o, float* part_ml, float* logits, void* stream) {
-    const Layer* ls = (const Layer*)layers_host;
-    const int Nq = Hq * hd, Nkv = Hkv * hd, Nqkv = Nq + 2 * Nkv;
+    const StepCtx c = step_ctx(layers_host, L, B, H, Hq, Hkv, hd, F, V, eps, E, norm_w, tok, embed_done, x, qkv, o, h, act, ss_ws, nss, logits, stream);
     const int nchunk = (cur_len + 1 + 63) / 64;
-    int rc;
-#define CK(call) do { rc = (call); if (rc) return rc; } while (0)
-    const StepGemms sg = step_gemms(ss_ws, nss, B, H, Nq, Nqkv, F, V, eps, stream);
-    if (!(embed_done && sg.v2)) {          // else bra_sample_embed already left x = E[tok] and its RMSNorm statistics
-        CK(bra_embed_scatter_fwd(tok, nullptr, E, H, nullptr, 0, x, H, B, H, stream));
-        CK(sg_begin(sg, x));
-    }
-    for (int li = 0; li < L; ++li) {
-        const Layer& l = ls[li];
-        CK(sg_qkv(sg, l, x, qkv));
-        CK(bra_dec_attn_partial(qkv, Nqkv, l.qn, l.kn, cosT, sinT, pos, l.kc, l.vc, kmask, part_o, part_ml, B, Hq, Hkv, hd,
-                                Smax, cur_len, eps, scale, 0, 0, len_dev, stream));
-        CK(bra_attn_decode_merge(part_o, part_ml, o, B, Hq, hd, nchunk, len_dev, 0, stream));
-        CK(sg_tail(sg, l, o, x, h, act));
-    }
-    if (logits) CK(sg_head(sg, x, norm_w, E, L > 0 ? ls[0].head_packed : nullptr, L > 0 ? (ls[0].flags & 4) : 0, logits, L > 0 ? ls[0].head_tmax : nullptr, (L > 0 && (ls[0].flags & 16)) ? ls[0].sc_head : nullptr));
-#undef CK
-    return 0;
+    return run_step(c, [&](const Layer& l) -> int {
+        const int rc = bra_dec_attn_partial(qkv, c.sg.Nqkv, l.qn, l.kn, cosT, sinT, pos, l.kc, l.vc, kmask, part_o, part_ml, B, Hq, Hkv, hd,
+                                            Smax, cur_len, eps, scale, 0, 0, len_dev, stream);
+        return rc ? rc : bra_attn_decode_merge(part_o, part_ml, o, B, Hq, hd, nchunk, len_dev, 0, stream);
+    });
 }
-
 
 // Shared-prefix variant: the B = R * copies sequences are grouped by prompt; the prompt part of the attention reads
 // ONE copy of the prompt K / V^T (bra_dec_attn_shared), the completion part the per-sequence completion cache
@@ -178,29 +204,15 @@ extern "C" int bra_qwen_decode_step_shared(const void* layers_host, int L, int R
                                            const void* norm_w, const float* cosT, const float* sinT, const int* tok,
                                            const int* pos, const void* pmask, int t, const int* t_dev, int embed_done, void* x, void* qkv, void* o,
                                            void* h, void* act, float* ss_ws, int nss, float* part_o, float* part_ml, float* logits, void* stream) {
-    const Layer* ls = (const Layer*)layers_host;
     const int B = R * copies;
-    const int Nq = Hq * hd, Nkv = Hkv * hd, Nqkv = Nq + 2 * Nkv;
+    const StepCtx c = step_ctx(layers_host, L, B, H, Hq, Hkv, hd, F, V, eps, E, norm_w, tok, embed_done, x, qkv, o, h, act, ss_ws, nss, logits, stream);
     const int npc = (P + 63) / 64, ncc = (t + 1 + 63) / 64, ntot = npc + ncc;
-    int rc;
-#define CK(call) do { rc = (call); if (rc) return rc; } while (0)
-    const StepGemms sg = step_gemms(ss_ws, nss, B, H, Nq, Nqkv, F, V, eps, stream);
-    if (!(embed_done && sg.v2)) {          // else bra_sample_embed already left x = E[tok] and its RMSNorm statistics
-        CK(bra_embed_scatter_fwd(tok, nullptr, E, H, nullptr, 0, x, H, B, H, stream));
-        CK(sg_begin(sg, x));
-    }
-    for (int li = 0; li < L; ++li) {
-        const Layer& l = ls[li];
-        CK(sg_qkv(sg, l, x, qkv));
-        CK(bra_dec_attn_both(qkv, Nqkv, l.qn, l.kn, cosT, sinT, pos, l.kp, (long)Hkv * P * hd, (long)P * hd, (long)hd, l.vtp,
-                             (long)Hkv * hd * vt_pitch, (long)hd * vt_pitch, vt_pitch, pmask, l.kc, l.vc, part_o, part_ml, R,
-                             copies, Hq, Hkv, hd, P, C, t, eps, scale, t_dev, L > 0 ? ls[0].rope_rows : nullptr, stream));
-        CK(bra_attn_decode_merge(part_o, part_ml, o, B, Hq, hd, ntot, t_dev, npc, stream));
-        CK(sg_tail(sg, l, o, x, h, act));
-    }
-    if (logits) CK(sg_head(sg, x, norm_w, E, L > 0 ? ls[0].head_packed : nullptr, L > 0 ? (ls[0].flags & 4) : 0, logits, L > 0 ? ls[0].head_tmax : nullptr, (L > 0 && (ls[0].flags & 16)) ? ls[0].sc_head : nullptr));
-#undef CK
-    return 0;
+    return run_step(c, [&](const Layer& l) -> int {
+        const int rc = bra_dec_attn_both(qkv, c.sg.Nqkv, l.qn, l.kn, cosT, sinT, pos, l.kp, (long)Hkv * P * hd, (long)P * hd, (long)hd, l.vtp,
+                                         (long)Hkv * hd * vt_pitch, (long)hd * vt_pitch, vt_pitch, pmask, l.kc, l.vc, part_o, part_ml, R,
+                                         copies, Hq, Hkv, hd, P, C, t, eps, scale, t_dev, c.rope_rows, stream);
+        return rc ? rc : bra_attn_decode_merge(part_o, part_ml, o, B, Hq, hd, ntot, t_dev, npc, stream);
+    });
 }
 
 // Shared-prefix variant on k_decattn.hip (bra_dec_attn_one: items kernel + merge kernel): 6 launches per layer.  The layer
@@ -211,27 +223,12 @@ extern "C" int bra_qwen_decode_step_one(const void* layers_host, int L, int R, i
                                         const int* pos, const void* pmask, int t, const int* t_dev, int embed_done, void* x, void* qkv, void* o,
                                         void* h, void* act, float* ss_ws, int nss, float* part_o, float* part_ml, int nslot,
                                         float* logits, void* stream) {
-    const Layer* ls = (const Layer*)layers_host;
-    const int B = R * copies;
-    const int Nq = Hq * hd, Nkv = Hkv * hd, Nqkv = Nq + 2 * Nkv;
-    int rc;
-#define CK(call) do { rc = (call); if (rc) return rc; } while (0)
-    const StepGemms sg = step_gemms(ss_ws, nss, B, H, Nq, Nqkv, F, V, eps, stream);
-    if (!(embed_done && sg.v2)) {          // else bra_sample_embed already left x = E[tok] and its RMSNorm statistics
-        CK(bra_embed_scatter_fwd(tok, nullptr, E, H, nullptr, 0, x, H, B, H, stream));
-        CK(sg_begin(sg, x));
-    }
-    for (int li = 0; li < L; ++li) {
-        const Layer& l = ls[li];
-        CK(sg_qkv(sg, l, x, qkv));
-        CK(bra_dec_attn_one(qkv, Nqkv, l.qn, l.kn, cosT, sinT, pos, L > 0 ? ls[0].rope_rows : nullptr, l.kp, (long)Hkv * P * hd,
-                            (long)P * hd, (long)hd, l.vtp, (long)Hkv * hd * vt_pitch, (long)hd * vt_pitch, vt_pitch, pmask, l.kc, l.vc, cp,
-                            part_o, part_ml, nslot, o, Nq, R, copies, Hq, Hkv, hd, P, C, t, eps, scale, t_dev, stream));
-        CK(sg_tail(sg, l, o, x, h, act));
-    }
-    if (logits) CK(sg_head(sg, x, norm_w, E, L > 0 ? ls[0].head_packed : nullptr, L > 0 ? (ls[0].flags & 4) : 0, logits, L > 0 ? ls[0].head_tmax : nullptr, (L > 0 && (ls[0].flags & 16)) ? ls[0].sc_head : nullptr));
-#undef CK
-    return 0;
+    const StepCtx c = step_ctx(layers_host, L, R * copies, H, Hq, Hkv, hd, F, V, eps, E, norm_w, tok, embed_done, x, qkv, o, h, act, ss_ws, nss, logits, stream);
+    return run_step(c, [&](const Layer& l) -> int {
+        return bra_dec_attn_one(qkv, c.sg.Nqkv, l.qn, l.kn, cosT, sinT, pos, c.rope_rows, l.kp, (long)Hkv * P * hd, (long)P * hd, (long)hd, l.vtp,
+                                (long)Hkv * hd * vt_pitch, (long)hd * vt_pitch, vt_pitch, pmask, l.kc, l.vc, cp, part_o, part_ml, nslot, o, c.sg.Nq,
+                                R, copies, Hq, Hkv, hd, P, C, t, eps, scale, t_dev, stream);
+    });
 }
 
 #ifdef BRA_DEBUG      // the persistent decode step is an opt-in experiment: libbioreason_hip_debug.so only
@@ -246,35 +243,31 @@ extern "C" int bra_qwen_decode_step_persist(const void* layers_host, const void*
                                             void* qkv, void* o, void* h, void* act, float* ss_ws, int nss, float* part_o,
                                             float* part_ml, int nslot, float* logits, void* sync, int prefetch, int stop_after,
                                             int timeout_us, void* stream) {
-    const Layer* ls = (const Layer*)layers_host;
-    const int B = R * copies;
-    const int Nq = Hq * hd, Nkv = Hkv * hd, Nqkv = Nq + 2 * Nkv;
+    const StepCtx c = step_ctx(layers_host, L, R * copies, H, Hq, Hkv, hd, F, V, eps, E, norm_w, tok, embed_done, x, qkv, o, h, act, ss_ws, nss, logits, stream);
+    const StepGemms& sg = c.sg;
     int rc;
 #define CK(call) do { rc = (call); if (rc) return rc; } while (0)
-    const StepGemms sg = step_gemms(ss_ws, nss, B, H, Nq, Nqkv, F, V, eps, stream);
-    if (!sg.v2 || L <= 0 || !(ls[0].flags & 1) || !(ls[0].flags & 2)) return BRA_ERR_UNSUPPORTED;     // packed + folded weights only
-    if (!(embed_done && sg.v2)) {
-        CK(bra_embed_scatter_fwd(tok, nullptr, E, H, nullptr, 0, x, H, B, H, stream));
-        CK(sg_begin(sg, x));
-    }
+    if (!sg.v2 || L <= 0 || !(c.ls[0].flags & 1) || !(c.ls[0].flags & 2)) return BRA_ERR_UNSUPPORTED;     // packed + folded weights only
+    CK(step_begin(c));
+    // the persistent kernel over the `n` records at `table` of the device table
+    auto persist = [&](const void* table, int n, int pf, int stop) -> int {
+        return bra_qwen_layers_persist(table, n, R, copies, H, Hq, Hkv, hd, F, P, vt_pitch, C, cp, eps, scale, cosT, sinT, pos, c.rope_rows,
+                                       pmask, t, t_dev, x, qkv, o, h, act, ss_ws, nss, part_o, part_ml, nslot, sync, pf, stop, timeout_us,
+                                       stream);
+    };
     if (stop_after <= -100) {
         // diagnostics: phase by phase, the ops whose mask bit is set (1 qkv, 2 attention, 4 o, 8 gate/up, 16 down) by the LAUNCHED
         // kernels, the others by single-phase windows of the persistent kernel — localises a numerical difference between the two
         const int mask = -stop_after - 100;
-        char* ld = (char*)layers_dev;
+        const char* ld = (const char*)layers_dev;
         const int rec = bra_persist_layer_desc_size();
         for (int li = 0; li < L; ++li) {
-            const Layer& l = ls[li];
-            auto win = [&](int p0, int p1) -> int {        // phases [p0, p1) of layer li on a one-layer table
-                return bra_qwen_layers_persist(ld + (long)li * rec, 1, R, copies, H, Hq, Hkv, hd, F, P, vt_pitch, C, cp, eps, scale, cosT,
-                                               sinT, pos, ls[0].rope_rows, pmask, t, t_dev, x, qkv, o, h, act, ss_ws, nss, part_o,
-                                               part_ml, nslot, sync, 0, -1000 - (p0 * 8 + p1), timeout_us, stream);
-            };
+            const Layer& l = c.ls[li];
+            auto win = [&](int p0, int p1) -> int { return persist(ld + (long)li * rec, 1, 0, -1000 - (p0 * 8 + p1)); };      // phases [p0, p1) of layer li
             if (mask & 1) CK(sg_qkv(sg, l, x, qkv)); else CK(win(0, 1));
-            if (mask & 2) CK(bra_dec_attn_one(qkv, Nqkv, l.qn, l.kn, cosT, sinT, pos, ls[0].rope_rows, l.kp, (long)Hkv * P * hd,
-                                              (long)P * hd, (long)hd, l.vtp, (long)Hkv * hd * vt_pitch, (long)hd * vt_pitch, vt_pitch, pmask,
-                                              l.kc, l.vc, cp, part_o, part_ml, nslot, o, Nq, R, copies, Hq, Hkv, hd, P, C, t, eps, scale,
-                                              t_dev, stream));
+            if (mask & 2) CK(bra_dec_attn_one(qkv, sg.Nqkv, l.qn, l.kn, cosT, sinT, pos, c.rope_rows, l.kp, (long)Hkv * P * hd, (long)P * hd,
+                                              (long)hd, l.vtp, (long)Hkv * hd * vt_pitch, (long)hd * vt_pitch, vt_pitch, pmask, l.kc, l.vc, cp,
+                                              part_o, part_ml, nslot, o, sg.Nq, R, copies, Hq, Hkv, hd, P, C, t, eps, scale, t_dev, stream));
             else CK(win(1, 3));
             const int pk = l.flags & 1;
             if (mask & 4) CK(bra_dec_gemm2_packed(o, sg.Nq, nullptr, 0, nullptr, 0.f, l.Wo, sg.Nq, x, sg.H, h, sg.H, sg.ssh, sg.nss, sg.B, sg.H, sg.Nq, 0, 0, pk, stream));
@@ -285,11 +278,8 @@ extern "C" int bra_qwen_decode_step_persist(const void* layers_host, const void*
             else CK(win(5, 6));
         }
     } else
-    CK(bra_qwen_layers_persist(layers_dev, L, R, copies, H, Hq, Hkv, hd, F, P, vt_pitch, C, cp, eps, scale, cosT, sinT, pos,
-                               ls[0].rope_rows, pmask, t, t_dev, x, qkv, o, h, act, ss_ws, nss, part_o, part_ml, nslot, sync,
-                               prefetch, stop_after, timeout_us, stream));
-    if (logits) CK(sg_head(sg, x, norm_w, E, ls[0].head_packed, ls[0].flags & 4, logits, ls[0].head_tmax, (ls[0].flags & 16) ? ls[0].sc_head : nullptr));
+        CK(persist(layers_dev, L, prefetch, stop_after));
 #undef CK
-    return 0;
+    return step_head(c);
 }
 #endif  // BRA_DEBUG

@@ -24,6 +24,26 @@ from ._lib import current_stream, get_lib
 from .engine import BF16, QwenEngine, SeqMeta, _nullctx
 
 
+# Host switches of the token loop and of the prompt pass in front of it (environment variable -> default), all read through
+# _switch() while a rollout is set up — by generate(), prefill() and the step states' constructors — and never per token.
+_SWITCHES = {
+    "BRA_DEC_PACK": "1",            # 0: row-major rollout weights (plain-layout bra_dec_gemm2), as where the packer refuses a shape
+    "BRA_DEC_PACK_HEAD": "1",       # 0: row-major lm_head at <= 8 sequences
+    "BRA_DEC_GEMM_V1": "0",         # 1: first-generation projections (bra_dec_gemm), as where the hidden size needs > 256 statistics columns
+    "BRA_DEC_ATTN": "one",          # both: first-generation shared-prefix attention (bra_dec_attn_both + merge)
+    "BRA_DEC_ROWS32": "0",          # 1: 17 .. 32 sequences in one token loop
+    "BRA_DEC_PERSIST": "0",         # 1 .. 3: persistent step (debug library), prefetch level 0 .. 2
+    "BRA_DEC_PERSIST_STOP": "0",    # its diagnostics (bra_qwen_decode_step_persist: stop_after)
+    "BRA_SAMPLE_TILES": "1",        # 0: full-scan sampler
+    "BRA_PREFILL_CHUNKS": "1",      # 2: two-chunk prompt pass for wide prompts
+    "BRA_PREFILL_CHUNKS_FORCE": "",  # 2: ... for any prompt of >= 2 rows (tests)
+}
+
+
+def _switch(name: str) -> str:
+    return os.environ.get(name, _SWITCHES[name])
+
+
 class KVCache:
     def __init__(self, eng: QwenEngine, B: int, Smax: int, device):
         self.k = [torch.zeros((B, eng.Hkv, Smax, eng.hd), dtype=BF16, device=device) for _ in range(eng.L)]
@@ -51,8 +71,8 @@ def prefill(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, ca
     # on the same rows: every row's result is the one-chunk result (rows of a GEMM are independent, a query visits its key tiles in
     # the same order).  Measured at one prompt of 2180 rows (round 4, tools/decode_probe.py): 16.0 ms against 15.6 ms for one chain —
     # the half-height GEMMs lose what the overlap gains — so it is OPT-IN (BRA_PREFILL_CHUNKS=2), kept for wider prompts.
-    two = (dev.type == "cuda" and os.environ.get("BRA_PREFILL_CHUNKS", "1") == "2" and B * S <= 4096 and S >= 1024)
-    if two or (os.environ.get("BRA_PREFILL_CHUNKS_FORCE") == "2" and S >= 2):
+    two = (dev.type == "cuda" and _switch("BRA_PREFILL_CHUNKS") == "2" and B * S <= 4096 and S >= 1024)
+    if two or (_switch("BRA_PREFILL_CHUNKS_FORCE") == "2" and S >= 2):
         Sa = (S // 2 + 63) // 64 * 64 if S >= 256 else max(1, S // 2)
         posm = pos.reshape(B, S)
         ma = SeqMeta(B=B, S=Sa, pos=posm[:, :Sa].reshape(-1).contiguous(), kmask=kmask[:, :Sa].contiguous(), lora_on=model._lora_enabled,
@@ -165,12 +185,11 @@ def rollout_weights(model, rows: int = 8):
     interleaved in blocks of 8 for the SwiGLU epilogue.  Rebuilt when the adapters or base weights changed."""
     eng: QwenEngine = model.ensure_packed()
     arena = model.arena
-    pack = os.environ.get("BRA_DEC_PACK", "1") == "1"
-    fold = pack and os.environ.get("BRA_DEC_FOLD", "1") == "1"
+    pack = _switch("BRA_DEC_PACK") == "1"
     wide = rows > 8             # 9 .. 32 sequences: every projection is packed for 16-column tiles (ops.dec_pack_weights(rows=16));
     #                             the 32-row projections stream the same image — there is no second copy of the rollout weights
-    fp8 = rollout_fp8_enabled(model) and pack and fold and not wide
-    key = (model._packed_sig, model._lora_enabled, pack, fold, wide, fp8, None if arena is None or arena.params is None else (arena.step_count, arena.params._version))
+    fp8 = rollout_fp8_enabled(model) and pack and not wide
+    key = (model._packed_sig, model._lora_enabled, pack, wide, fp8, None if arena is None or arena.params is None else (arena.step_count, arena.params._version))
     cached = getattr(eng, "_rollout", None)
     if cached is not None and cached[0] == key:
         return cached[1]
@@ -187,10 +206,10 @@ def rollout_weights(model, rows: int = 8):
         rec = {"Wqkv": merged(L.Wqkv, L.lora["qkv"]), "Wo": merged(L.Wo, L.lora["o"]), "Wgu": wgu_il,
                "Wd": merged(L.Wd, L.lora["d"])}
         if pack:
-            # fragment order of the M <= 8 streaming projections: contiguous KiB per wave-instruction (k_decgemm.hip)
-            # (and, `fold`, the RMSNorm weight of the projection's input multiplied in: the kernel then applies rstd to the reduced
-            # products and loads no norm weights / statistics ahead of its MFMAs)
-            nws = {"Wqkv": L.ln1 if fold else None, "Wgu": L.ln2 if fold else None, "Wo": None, "Wd": None}
+            # fragment order of the M <= 8 streaming projections: contiguous KiB per wave-instruction (k_decgemm.hip), with the
+            # RMSNorm weight of the projection's input multiplied in: the kernel then applies rstd to the reduced products and
+            # loads no norm weights / statistics ahead of its MFMAs
+            nws = {"Wqkv": L.ln1, "Wgu": L.ln2, "Wo": None, "Wd": None}
             if fp8:
                 # opt-in fp8 rollout weights (BASELINE config 5): e4m3 + one fp32 scale per output row of the MERGED, norm-folded weight;
                 # a layer whose shapes the fp8 kernel does not take keeps bf16 (all four projections together)
@@ -198,7 +217,7 @@ def rollout_weights(model, rows: int = 8):
                 if all(v is not None for v in q8.values()):
                     for nm, (q, sc) in q8.items():
                         rec[nm + "_q"], rec[nm + "_s"] = q, sc
-                    rec["fp8"], rec["folded"] = True, True
+                    rec["fp8"] = True
                     if fp8_prefill_enabled() and eng.fp8_supported():
                         # the same quantised weights, row-major, for the prompt pass on the fp8 MFMA path (engine._layer_fwd_fp8):
                         # same rule and rounding as the fragment-ordered image above ([gate; up] rows not interleaved there)
@@ -212,7 +231,6 @@ def rollout_weights(model, rows: int = 8):
                   for nm in ("Wqkv", "Wo", "Wgu", "Wd")}
             if all(v is not None for v in pk.values()):
                 rec.update({nm + "_p": v for nm, v in pk.items()})
-                rec["folded"] = fold
         out.append(rec)
     eng._rollout = (key, out)
     return out
@@ -250,54 +268,68 @@ def packed_head_fp8(model):
 
 
 def packed_head(model):
-    """fragment-packed copy of the tied lm_head / embedding matrix for the decode step's logits projection (622 MB at
-    Qwen3-1.7B); the matrix is frozen under LoRA training, so the copy is rebuilt only when its storage changes"""
+    """fragment-packed copy of the tied lm_head / embedding matrix, final RMSNorm weight folded in, for the decode step's logits
+    projection (622 MB at Qwen3-1.7B), or None where the packer refuses the shape; the matrix is frozen under LoRA training, so the copy is rebuilt only when its storage changes"""
     eng: QwenEngine = model.ensure_packed()
-    fold = os.environ.get("BRA_DEC_FOLD", "1") == "1"
-    key = (eng.E.data_ptr(), eng.E._version, tuple(eng.E.shape), eng.norm_w.data_ptr(), eng.norm_w._version, fold)
+    key = (eng.E.data_ptr(), eng.E._version, tuple(eng.E.shape), eng.norm_w.data_ptr(), eng.norm_w._version)
     cached = getattr(eng, "_head_packed", None)
     if cached is None or cached[0] != key:
-        eng._head_packed = (key, ops.dec_pack_weights(eng.E, out_f32=True, norm_w=eng.norm_w if fold else None), fold)
-    return eng._head_packed[1], eng._head_packed[2]
+        eng._head_packed = (key, ops.dec_pack_weights(eng.E, out_f32=True, norm_w=eng.norm_w))
+    return eng._head_packed[1]
 
 
-class FusedDecodeState:
-    """Descriptor table + workspaces for `bra_qwen_decode_step_fused` (6 launches per layer, logits included)."""
+class _FusedStepState:
+    """What the two fused step states share: the rollout weight set and the statistics workspace, the layer table (norm weights,
+    projection images, the caches handed in per layer), the lm_head image of record 0, the bf16 row buffers, the attention partials
+    for `nslot` slots per (sequence, q-head) and the rope tables for `rope_len` positions."""
 
-    def __init__(self, model, cache: KVCache, B: int):
+    def __init__(self, model, B: int, kc, vc, nslot: int, rope_len: int, kp=None, vtp=None, rope_rows: bool = False):
         eng: QwenEngine = model.engine
         dev = eng.device
-        self.eng, self.cache, self.B = eng, cache, B
+        self.eng, self.B = eng, B
         self.rw = rollout_weights(model, rows=B)
-        self.ss_ws, self.nss = _norm_stat_ws(eng, eng.device, rows=B)
-        use_packed = self.ss_ws is not None and _packed_ok(B, self.rw)
+        self.ss_ws, self.nss = _norm_stat_ws(eng, dev, rows=B)
+        self.use_packed = use_packed = self.ss_ws is not None and _packed_ok(B, self.rw)
         arr = _layer_table(eng.L)
         for i, (L, R) in enumerate(zip(eng.layers, self.rw)):
             d = arr[i]
             d.ln1, d.ln2, d.qn, d.kn = L.ln1.data_ptr(), L.ln2.data_ptr(), L.qn.data_ptr(), L.kn.data_ptr()
             _set_proj(d, R, use_packed)
-            d.kc, d.vc = cache.k[i].data_ptr(), cache.v[i].data_ptr()
-        if use_packed and (B > 8 or os.environ.get("BRA_DEC_PACK_HEAD", "1") == "1"):      # (above 8 rows only the packed head streams)
-            h8 = packed_head_fp8(model) if (B <= 8 and all(R_.get("fp8") for R_ in self.rw)) else None
+            d.kc, d.vc = kc[i].data_ptr(), vc[i].data_ptr()
+            if kp is not None:
+                d.kp, d.vtp = kp[i].data_ptr(), vtp[i].data_ptr()
+        if use_packed and (B > 8 or _switch("BRA_DEC_PACK_HEAD") == "1"):      # (above 8 rows only the packed head streams)
+            h8 = packed_head_fp8(model) if (B <= 8 and all(R.get("fp8") for R in self.rw)) else None
             if h8 is not None:
                 self.head_p, self.head_s = h8
                 arr[0].head_packed, arr[0].sc_head = self.head_p.data_ptr(), self.head_s.data_ptr()
                 arr[0].flags |= 4 | 16
             else:
-                self.head_p, head_folded = packed_head(model)
+                self.head_p = packed_head(model)
                 if self.head_p is not None:
                     arr[0].head_packed = self.head_p.data_ptr()
-                    arr[0].flags |= 4 if head_folded else 0
+                    arr[0].flags |= 4
+        # (cos | sin) rows of every sequence's current position, refreshed once per token by bra_advance_counters or the sampler
+        self.rope_rows = torch.zeros((B, eng.hd), dtype=torch.float32, device=dev) if rope_rows else None
+        if rope_rows:
+            arr[0].rope_rows = self.rope_rows.data_ptr()
         self.arr = arr
 
         def buf(n):
             return torch.empty((B, n), dtype=BF16, device=dev)
 
         self.x, self.h, self.qkv, self.o, self.act = buf(eng.H), buf(eng.H), buf(eng.Nq + 2 * eng.Nkv), buf(eng.Nq), buf(eng.F)
-        nch = (cache.Smax + 63) // 64
-        self.part_o = torch.empty((B, eng.Hq, nch, eng.hd), dtype=torch.float32, device=dev)
-        self.part_ml = torch.empty((B, eng.Hq, nch, 2), dtype=torch.float32, device=dev)
-        self.cosT, self.sinT = eng.rope(cache.Smax + 1)
+        self.part_o = torch.empty((B, eng.Hq, nslot, eng.hd), dtype=torch.float32, device=dev)
+        self.part_ml = torch.empty((B, eng.Hq, nslot, 2), dtype=torch.float32, device=dev)
+        self.cosT, self.sinT = eng.rope(rope_len)
+
+
+class FusedDecodeState(_FusedStepState):
+    """Descriptor table + workspaces for `bra_qwen_decode_step_fused` (6 launches per layer, logits included)."""
+
+    def __init__(self, model, cache: KVCache, B: int):
+        self.cache = cache
+        super().__init__(model, B, cache.k, cache.v, (cache.Smax + 63) // 64, cache.Smax + 1)
 
     def step(self, tok, pos, kmask, cur_len: int, logits: torch.Tensor, len_dev=None, embed_done: bool = False):
         """`len_dev` (device int32 [1] holding cur_len): the kernels read the length from memory and `cur_len` only
@@ -316,7 +348,7 @@ def decode_slots(P: int, C: int) -> int:
     return (P + 63) // 64 + (C + 63) // 64 + 1
 
 
-class SharedDecodeState:
+class SharedDecodeState(_FusedStepState):
     """`bra_qwen_decode_step_shared`: R prompts x `copies` sequences; prompt K / V^T are held once per prompt, each
     sequence owns only a completion cache [Hkv, C, hd]."""
 
@@ -328,14 +360,13 @@ class SharedDecodeState:
         eng: QwenEngine = model.engine
         dev = eng.device
         B = R * copies
-        self.eng, self.R, self.copies, self.P, self.C, self.B = eng, R, copies, P, C, B
-        self.rw = rollout_weights(model, rows=B)
+        self.R, self.copies, self.P, self.C = R, copies, P, C
         self.kp, self.vtp = cache_r.k, vtp                       # [R,Hkv,P,hd], [R,Hkv,hd,pitch]
         self.kc = [torch.zeros((B, eng.Hkv, C, eng.hd), dtype=BF16, device=dev) for _ in range(eng.L)]
         # attention of the step: "one" = bra_dec_attn_one (k_decattn.hip: MFMA for the completion keys too, transposed completion
         # V cache [B, Hkv, hd, cp], the new key as its own partial);  "both" = bra_dec_attn_both + bra_attn_decode_merge
         # (first generation: row-layout V cache, completion keys on the VALU)
-        self.attn_impl = os.environ.get("BRA_DEC_ATTN", "one")
+        self.attn_impl = _switch("BRA_DEC_ATTN")
         nslot = decode_slots(P, C)
         if self.attn_impl == "one" and nslot > 256:
             self.attn_impl = "both"
@@ -345,58 +376,25 @@ class SharedDecodeState:
         else:
             self.vc = [torch.zeros((B, eng.Hkv, C, eng.hd), dtype=BF16, device=dev) for _ in range(eng.L)]
         self.vt_pitch = vtp[0].shape[-1]
-        self.ss_ws, self.nss = _norm_stat_ws(eng, dev, rows=B)
-        use_packed = self.ss_ws is not None and _packed_ok(B, self.rw)
-        arr = _layer_table(eng.L)
-        for i, (L, Rw) in enumerate(zip(eng.layers, self.rw)):
-            d = arr[i]
-            d.ln1, d.ln2, d.qn, d.kn = L.ln1.data_ptr(), L.ln2.data_ptr(), L.qn.data_ptr(), L.kn.data_ptr()
-            _set_proj(d, Rw, use_packed)
-            d.kc, d.vc = self.kc[i].data_ptr(), self.vc[i].data_ptr()
-            d.kp, d.vtp = self.kp[i].data_ptr(), self.vtp[i].data_ptr()
-        if use_packed and (B > 8 or os.environ.get("BRA_DEC_PACK_HEAD", "1") == "1"):
-            h8 = packed_head_fp8(model) if (B <= 8 and all(R_.get("fp8") for R_ in self.rw)) else None
-            if h8 is not None:
-                self.head_p, self.head_s = h8
-                arr[0].head_packed, arr[0].sc_head = self.head_p.data_ptr(), self.head_s.data_ptr()
-                arr[0].flags |= 4 | 16
-            else:
-                self.head_p, head_folded = packed_head(model)
-                if self.head_p is not None:
-                    arr[0].head_packed = self.head_p.data_ptr()
-                    arr[0].flags |= 4 if head_folded else 0
-        # (cos | sin) rows of every sequence's current position, refreshed once per token by bra_advance_counters
-        self.rope_rows = torch.zeros((B, eng.hd), dtype=torch.float32, device=dev) if os.environ.get("BRA_DEC_ROPE_ROWS", "1") == "1" else None
-        if self.rope_rows is not None:
-            arr[0].rope_rows = self.rope_rows.data_ptr()
-        self.arr = arr
-
-        def buf(n):
-            return torch.empty((B, n), dtype=BF16, device=dev)
-
-        self.x, self.h, self.qkv, self.o, self.act = buf(eng.H), buf(eng.H), buf(eng.Nq + 2 * eng.Nkv), buf(eng.Nq), buf(eng.F)
-        nch = (P + 63) // 64 + (C + 63) // 64 + 1
-        self.part_o = torch.empty((B, eng.Hq, nch, eng.hd), dtype=torch.float32, device=dev)
-        self.part_ml = torch.empty((B, eng.Hq, nch, 2), dtype=torch.float32, device=dev)
-        self.cosT, self.sinT = eng.rope(P + C + 1)
+        super().__init__(model, B, self.kc, self.vc, nslot, P + C + 1, kp=self.kp, vtp=self.vtp, rope_rows=True)
         # persistent form of the layer loop (k_persist.hip): ONE launch for all decoder layers, bit-identical to the launched path.
         # BRA_DEC_PERSIST: "0" (default) launched kernels; "1" / "2" / "3" opt into the persistent step with prefetch level 0 / 1 / 2
         # where the kernel is instantiated for the shape (<= 8 sequences, packed + folded weights, one CU per workgroup) — measured
         # slower than the launched step.  `sync` is zeroed here, once per rollout: the kernel's error word is
         # sticky across the token steps, so persist_timed_out() after the loop sees a timeout of ANY step
         self.persist = None
-        mode = os.environ.get("BRA_DEC_PERSIST", "0")
+        mode = _switch("BRA_DEC_PERSIST")
         if mode != "0" and not getattr(get_lib(), "debug", False):
             raise RuntimeError("BRA_DEC_PERSIST needs the debug library (the persistent decode step is not part of the product ABI): "
                                "call bioreason_amd._lib.use_debug_library() first (`make -C bioreason_amd/csrc debug`)")
-        if mode != "0" and self.attn_impl == "one" and use_packed and B <= 8 and all(Rw.get("folded") and not Rw.get("fp8") for Rw in self.rw) and dev.type == "cuda":
+        if mode != "0" and self.attn_impl == "one" and self.use_packed and B <= 8 and not any(Rw.get("fp8") for Rw in self.rw) and dev.type == "cuda":
             tab = torch.tensor([[Rw["Wqkv_p"].data_ptr(), Rw["Wo_p"].data_ptr(), Rw["Wgu_p"].data_ptr(), Rw["Wd_p"].data_ptr(),
                                  L.qn.data_ptr(), L.kn.data_ptr(), self.kp[i].data_ptr(), self.vtp[i].data_ptr(),
                                  self.kc[i].data_ptr(), self.vc[i].data_ptr()] for i, (L, Rw) in enumerate(zip(eng.layers, self.rw))],
                                dtype=torch.int64)
             assert tab.shape[1] * 8 == get_lib()._dll.bra_persist_layer_desc_size()
             self.persist = {"table": tab.contiguous(), "sync": torch.zeros(2048, dtype=torch.uint8, device=dev),       # (host table)
-                            "prefetch": max(0, int(mode) - 1), "ok": None}
+                            "prefetch": max(0, int(mode) - 1), "stop": int(_switch("BRA_DEC_PERSIST_STOP")), "ok": None}
 
     def step(self, tok, pos, pmask, t: int, logits: torch.Tensor, t_dev=None, embed_done: bool = False):
         e = self.eng
@@ -406,7 +404,7 @@ class SharedDecodeState:
                                    e.Hq, e.Hkv, e.hd, e.F, self.P, self.vt_pitch, self.C, self.cp, e.V, e.eps, e.scale, e.E, e.norm_w,
                                    self.cosT, self.sinT, tok, pos, pmask, t, t_dev, int(embed_done), self.x, self.qkv, self.o, self.h,
                                    self.act, self.ss_ws, self.nss, self.part_o, self.part_ml, self.part_o.shape[2], logits, ps["sync"],
-                                   ps["prefetch"], int(os.environ.get("BRA_DEC_PERSIST_STOP", "0")), 50000, current_stream(self.x))
+                                   ps["prefetch"], ps["stop"], 50000, current_stream(self.x))
             if rc == 0:
                 ps["ok"] = True
                 return
@@ -425,28 +423,25 @@ class SharedDecodeState:
 
 
 def _set_proj(d, R, use_packed: bool):
-    """projection weight pointers of one layer record: the fragment-packed copies when the streaming kernels can take them"""
+    """projection weight pointers of one layer record: the fragment-packed, norm-folded copies when the streaming kernels can take
+    them (flags 1 | 2)"""
     sfx = "_p" if use_packed else ""
     d.Wqkv, d.Wo, d.Wgu, d.Wd = (R["Wqkv" + sfx].data_ptr(), R["Wo" + sfx].data_ptr(), R["Wgu" + sfx].data_ptr(),
                                   R["Wd" + sfx].data_ptr())
-    d.flags = (1 | (2 if R.get("folded") else 0)) if use_packed else 0
+    d.flags = 3 if use_packed else 0
     if use_packed and R.get("fp8"):                   # e4m3 images + row scales (bra_dec_gemm2_fp8)
         d.flags |= 8
         d.sc_qkv, d.sc_o, d.sc_gu, d.sc_d = R["Wqkv_s"].data_ptr(), R["Wo_s"].data_ptr(), R["Wgu_s"].data_ptr(), R["Wd_s"].data_ptr()
 
 
 def _packed_ok(B: int, rw) -> bool:
-    """the streaming projections (bra_dec_gemm2) take up to 32 rows; above 8 they need the norm-folded packed weights"""
-    if not all("Wqkv_p" in R for R in rw):
-        return False
-    return B <= 8 or (B <= MAX_DECODE_ROWS32 and all(R.get("folded") for R in rw))
+    """the streaming projections (bra_dec_gemm2) take up to 32 rows of the packed (and so norm-folded) weights"""
+    return B <= MAX_DECODE_ROWS32 and all("Wqkv_p" in R for R in rw)
 
 
 def _norm_stat_nss(eng) -> int:
-    """columns of the statistics workspace, or 0 where the second-generation projections do not apply"""
-    nblk = eng.H // 8 if (eng.H % 8 == 0 and (eng.H + 15) // 16 < 256 and eng.H // 8 <= 256) else (eng.H + 15) // 16
-    nss = (nblk + 31) // 32 * 32
-    return 0 if (nss > 256 or os.environ.get("BRA_DEC_GEMM_V1") == "1") else nss
+    """columns of the statistics workspace (bra_dec_stat_cols), or 0 where the second-generation projections do not apply"""
+    return 0 if _switch("BRA_DEC_GEMM_V1") == "1" else int(get_lib()._dll.bra_dec_stat_cols(int(eng.H)))
 
 
 def _norm_stat_ws(eng, dev, rows: int = 8):
@@ -503,30 +498,18 @@ def decode_rows_limit() -> int:
     """sequences one token loop takes: 16 — batches above 16 rows run as 16-row chunks, each with its own prefill, cache and loop —
     or, with BRA_DEC_ROWS32=1, 32 (one loop on the 32-row projections).  The one-loop path stays opt-in until it is measured against
     the previous commit on one box (NOTES.md, "32 rows per weight stream")"""
-    return MAX_DECODE_ROWS32 if os.environ.get("BRA_DEC_ROWS32", "0") == "1" else MAX_DECODE_ROWS
+    return MAX_DECODE_ROWS32 if _switch("BRA_DEC_ROWS32") == "1" else MAX_DECODE_ROWS
 
 
 def rows32_form_exists(K: int, normed: bool, packed: bool = True) -> bool:
-    """launch_dg2's rule (k_decgemm.hip) for 17 .. 32 rows over 16-column tiles of 32 k: does a 32-row kernel exist for this K?
-    The fast form (packed weights, K exactly one register round of the (waves, chunks) the launcher picks) always, except the
-    folded norm on 16 waves x 12 chunks; one clamped round outside the fast form up to waves x chunks = 64; K beyond one round
-    without norm only — packed on 16 waves x 8 chunks or on fewer waves, plain layout on fewer than 16 waves."""
-    if K <= 0 or K % 32:
-        return False
-    nsteps = K // 32
-    nw = 16 if nsteps >= 128 else (8 if nsteps >= 64 else 4)
-    spw = (nsteps + nw - 1) // nw
-    nl = 12 if (spw >= 12 and spw % 12 == 0) else (10 if (spw == 10 and nw == 8) else (8 if spw > 4 else 4))
-    if nsteps > nw * nl:
-        return (not normed) and ((nw < 16) or (nl == 8 and packed))
-    if packed and nsteps == nw * nl and not (normed and nw == 16 and nl == 12):
-        return True
-    return nw * nl <= 64
+    """does bra_dec_gemm2 have a 32-row kernel (17 .. 32 rows over 16-column tiles of 32 k) for this K?  The library's own answer
+    (bra_dec_gemm2_rows32_ok: the rule launch_dg2 dispatches by); `normed`: the folded norm, `packed`: fragment-ordered weights"""
+    return bool(get_lib()._dll.bra_dec_gemm2_rows32_ok(int(K), int(normed), int(packed)))
 
 
 def _one_loop_ok(model, B: int) -> bool:
     """17 .. 32 rows in ONE token loop: what the 32-row projections need is folded, bf16, fragment-packed rollout weights and the
-    second-generation statistics workspace; anything else (BRA_DEC_PACK / BRA_DEC_FOLD = 0, BRA_DEC_GEMM_V1, a shape the packer
+    second-generation statistics workspace; anything else (BRA_DEC_PACK = 0, BRA_DEC_GEMM_V1, a shape the packer
     refuses, fp8 rollout weights) keeps the 16-row chunks"""
     eng = model.ensure_packed()
     if _norm_stat_nss(eng) == 0 or rollout_fp8_enabled(model):      # (fp8 images stream against <= 8 rows: chunks, as before)
@@ -569,14 +552,63 @@ def _row_chunks(B: int, prompt_alias, max_rows: int = MAX_DECODE_ROWS):
     return chunks
 
 
+def _eos_ids(eos_token_id, pad_token_id):
+    """-> (eos, eos2, pad): the one or two EOS ids of the device-side sampler (-1 = none; an int or a list as HF takes it, the
+    first listed id is the pad default) and the id finished rows emit"""
+    eos2 = -1
+    if isinstance(eos_token_id, (list, tuple)):
+        ids_ = list(dict.fromkeys(int(e) for e in eos_token_id))
+        if len(ids_) > 2:
+            raise NotImplementedError("at most two eos_token_id values are supported by the device-side sampler")
+        eos2 = ids_[1] if len(ids_) > 1 else -1
+        eos_token_id = ids_[0] if ids_ else None
+    eos = -1 if eos_token_id is None else int(eos_token_id)
+    pad = int(pad_token_id) if pad_token_id is not None else (eos if eos >= 0 else 0)
+    return eos, eos2, pad
+
+
+def _prompt_pass(model, inputs_embeds, attention_mask, am, pos_prompt, prompt_alias, shared_grp, max_new_tokens: int):
+    """The prompt through the stack, once per DISTINCT prompt -> (last hidden rows [B, H], per-sequence KVCache or None,
+    SharedDecodeState or None, its prompt mask or None).  `shared_grp` (R, copies): the shared-prefix step decodes — the prompt K / V^T
+    stay one copy per prompt; None: every sequence gets its own cache rows."""
+    eng = model.engine
+    B, P, _ = inputs_embeds.shape
+    dev = inputs_embeds.device
+    Smax = P + max_new_tokens
+    if prompt_alias is None:
+        cache = KVCache(eng, B, Smax, dev)
+        return prefill(model, inputs_embeds, attention_mask, cache, pos_prompt, decode_rows=B), cache, None, None
+    # identical prompts (GRPO: the G copies of a prompt, grpo_trainer.py:107-116) are prefetched once: the rows of a
+    # batched forward are independent, so the K/V rows and the last hidden state of a copy equal its representative's
+    reps = sorted(set(prompt_alias))
+    where = {r: i for i, r in enumerate(reps)}
+    sel = torch.tensor(reps, device=dev)
+    gmap = torch.tensor([where[a] for a in prompt_alias], device=dev)
+    shared = pmask = cache = None
+    if shared_grp is not None:
+        # decode reads ONE copy of the prompt K / V^T per prompt (bra_dec_attn_shared); no per-copy replication
+        cache_r = KVCache(eng, len(reps), P, dev)
+        vtp = []
+        hid_r = prefill(model, inputs_embeds[sel], attention_mask[sel], cache_r, pos_prompt[sel], vt_sink=vtp, decode_rows=B)
+        shared = SharedDecodeState(model, cache_r, vtp, shared_grp[0], shared_grp[1], P, max_new_tokens)
+        pmask = am[sel].to(torch.uint8).contiguous()
+    else:
+        cache_r = KVCache(eng, len(reps), Smax, dev)
+        hid_r = prefill(model, inputs_embeds[sel], attention_mask[sel], cache_r, pos_prompt[sel], decode_rows=B)
+        cache = KVCache.__new__(KVCache)
+        cache.Smax = Smax
+        cache.k = [t.index_select(0, gmap) for t in cache_r.k]
+        cache.v = [t.index_select(0, gmap) for t in cache_r.v]
+        del cache_r
+    return hid_r.index_select(0, gmap).contiguous(), cache, shared, pmask
+
+
 def _generate_in_row_chunks(model, inputs_embeds, attention_mask, prompt_alias, force_tokens, eos_schedule, seed, kw, max_rows=MAX_DECODE_ROWS):
     """`kw`: EVERY other keyword of generate() (built from its locals, so a keyword added later is forwarded too)"""
     B = inputs_embeds.shape[0]
     trace = kw.pop("trace_logits", None)
     traces = []
-    eos_ = kw["eos_token_id"]
-    eos0 = (list(eos_)[0] if len(eos_) else None) if isinstance(eos_, (list, tuple)) else eos_
-    pad = int(kw["pad_token_id"]) if kw["pad_token_id"] is not None else (int(eos0) if eos0 is not None else 0)
+    pad = _eos_ids(kw["eos_token_id"], kw["pad_token_id"])[2]
     outs = []
     for ci, (lo, hi) in enumerate(_row_chunks(B, prompt_alias, max_rows)):
         alias = None
@@ -649,60 +681,26 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
             profile[name] = profile.get(name, 0.0) + (now - _t0[0]) * 1e3
             _t0[0] = now
 
-    eos2 = -1
-    if isinstance(eos_token_id, (list, tuple)):
-        ids_ = list(dict.fromkeys(int(e) for e in eos_token_id))
-        if len(ids_) > 2:
-            raise NotImplementedError("at most two eos_token_id values are supported by the device-side sampler")
-        eos2 = ids_[1] if len(ids_) > 1 else -1
-        eos_token_id = ids_[0] if ids_ else None
-    eos = -1 if eos_token_id is None else int(eos_token_id)
+    eos, eos2, pad = _eos_ids(eos_token_id, pad_token_id)
     if eos_schedule is not None:
         assert eos >= 0 and eos_schedule.dtype == torch.int32 and eos_schedule.numel() == inputs_embeds.shape[0]
-    pad = int(pad_token_id) if pad_token_id is not None else (eos if eos >= 0 else 0)
     Smax = P + max_new_tokens
     am = attention_mask.to(torch.long)
     pos_prompt = (am.cumsum(-1) - 1).masked_fill(am == 0, 0).to(torch.int32)      # TF:generation/utils.py:763-765
     kmask = torch.ones((B, Smax), dtype=torch.uint8, device=dev)
     kmask[:, :P] = am.to(torch.uint8)
-    shared = None
     grp = _uniform_groups(prompt_alias) if prompt_alias is not None else None
     # (more than 16 query rows per (prompt, kv-head) — Qwen3-4B: 8 rollouts x G = 4 — run as virtual prompts of <= 16 rows each in
     #  bra_dec_attn_one; the first-generation attention keeps the 16-row limit)
     G_ = eng.Hq // eng.Hkv
     # (SharedDecodeState falls back from "one" to the first-generation attention beyond 256 partial slots — P + C above ~16 K — and
     #  that one keeps the 16-row limit: such a batch takes the per-copy decode instead of failing in the kernel)
-    one_ok = os.environ.get("BRA_DEC_ATTN", "one") == "one" and decode_slots(P, max_new_tokens) <= 256
+    one_ok = _switch("BRA_DEC_ATTN") == "one" and decode_slots(P, max_new_tokens) <= 256
     rows_ok = grp is not None and (grp[1] * G_ <= 16 or (one_ok and G_ <= 16
                                                           and any(grp[1] % s_ == 0 and (grp[1] // s_) * G_ <= 16 for s_ in range(1, grp[1] + 1))))
     use_shared = (grp is not None and shared_prefix_decode and native_step and decode_impl == "fused" and eng.hd >= 64 and rows_ok)
-    if prompt_alias is None:
-        cache = KVCache(eng, B, Smax, dev)
-        hid = prefill(model, inputs_embeds, attention_mask, cache, pos_prompt, decode_rows=B)
-    else:
-        # identical prompts (GRPO: the G copies of a prompt, grpo_trainer.py:107-116) are prefetched once: the rows of a
-        # batched forward are independent, so the K/V rows and the last hidden state of a copy equal its representative's
-        reps = sorted(set(prompt_alias))
-        where = {r: i for i, r in enumerate(reps)}
-        sel = torch.tensor(reps, device=dev)
-        gmap = torch.tensor([where[a] for a in prompt_alias], device=dev)
-        if use_shared:
-            # decode reads ONE copy of the prompt K / V^T per prompt (bra_dec_attn_shared); no per-copy replication
-            cache_r = KVCache(eng, len(reps), P, dev)
-            vtp = []
-            hid_r = prefill(model, inputs_embeds[sel], attention_mask[sel], cache_r, pos_prompt[sel], vt_sink=vtp, decode_rows=B)
-            shared = SharedDecodeState(model, cache_r, vtp, grp[0], grp[1], P, max_new_tokens)
-            pmask = am[sel].to(torch.uint8).contiguous()
-            cache = None
-        else:
-            cache_r = KVCache(eng, len(reps), Smax, dev)
-            hid_r = prefill(model, inputs_embeds[sel], attention_mask[sel], cache_r, pos_prompt[sel], decode_rows=B)
-            cache = KVCache.__new__(KVCache)
-            cache.Smax = Smax
-            cache.k = [t.index_select(0, gmap) for t in cache_r.k]
-            cache.v = [t.index_select(0, gmap) for t in cache_r.v]
-            del cache_r
-        hid = hid_r.index_select(0, gmap).contiguous()
+    hid, cache, shared, pmask = _prompt_pass(model, inputs_embeds, attention_mask, am, pos_prompt, prompt_alias,
+                                              grp if use_shared else None, max_new_tokens)
     next_pos = (pos_prompt[:, -1] + 1).contiguous()                               # TF:generation/utils.py:979-984
     _tick("prefill")
 
@@ -729,7 +727,7 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
     # sampler over tile maxima (ops.sample_tiles): the lm_head epilogue of the fused step leaves the maximum of every 16-column
     # tile of the logits in `tmax`; the top-k stage then scans V / 16 maxima + 16 k logits instead of V logits (same tokens)
     ntile = (eng.V + 15) // 16
-    use_tiles = (dstate is not None and os.environ.get("BRA_SAMPLE_TILES", "1") == "1" and B <= 64 and ntile <= 8 * 4096
+    use_tiles = (dstate is not None and _switch("BRA_SAMPLE_TILES") == "1" and B <= 64 and ntile <= 8 * 4096
                  and (not do_sample or 1 <= top_k <= 64))
     tmax = None
     if use_tiles:
@@ -740,7 +738,7 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
     fuse_embed = (dstate is not None and dstate.ss_ws is not None and force_tokens is None and sample_ws is not None
                   and B <= MAX_DECODE_ROWS32 and (not do_sample or 1 <= top_k <= 64))     # (top_k = 0 / > 64: the general sampler, no fused gather)
     rope_args = None
-    if shared is not None and getattr(shared, "rope_rows", None) is not None:
+    if shared is not None:
         rope_args = (shared.cosT, shared.sinT, eng.hd, shared.rope_rows)
         ops.rope_rows(shared.cosT, shared.sinT, next_pos, eng.hd, shared.rope_rows)
     # issued launch by launch, the shared-prefix loop needs no device-side counters at all: the step index is a launch argument of

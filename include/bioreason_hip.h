@@ -268,6 +268,10 @@ int bra_dec_pack_weights(const void* W, long ldw, int N, int K, int act, int out
 int bra_dec_pack_weights_rows(const void* W, long ldw, int N, int K, int act, int out_f32, const void* norm_w, int rows, void* out,
                               void* stream);
 int bra_row_sumsq(const void* x, long ldx, int M, int K, float* ss, int nss, void* stream);
+/* plan: `nss` of a step at hidden size H (a multiple of 32), or 0 where the second-generation projections do not apply (more than 256) */
+int bra_dec_stat_cols(int H);
+/* plan: 1 if bra_dec_gemm2 / _packed have a 17 .. 32-row kernel for this K (`normed`: folded norm, `packed`: bit 0), else 0 */
+int bra_dec_gemm2_rows32_ok(int K, int normed, int packed);
 /* `t_dev` / `len_dev` (optional device int): when given, the attention kernels read the current length from it and
  * the host-side `cur_len` / `t` only size the grids (pass the maximum); the launch arguments are then identical for
  * every step, so one captured hipGraph replays the whole rollout (HF `_sample` loop, TF:generation/utils.py:2876-2925). */
