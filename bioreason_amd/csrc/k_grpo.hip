@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void topk_slices_kernel(const float* logits, l
 // first loads: read here they were two more memory round trips in the single-thread tail of every token).  Returns the token.
 __device__ inline int sample_pick(float* p, const float* top_v, const int* top_i, int k, int row, float temperature, float top_p,
                                   int do_sample, uint32_t seed, int step, int was_finished, uint8_t* finished, int pad_id, int eos_id,
-                                  int eos_id2, int* out_ids, float* out_logp, int* tokens_out, long ldt) {
+                                  int eos_id2, int* out_ids, float* out_logp, int* tokens_out, long ldt, float min_p) {
     int choice = top_i[0];
     float lp = 0.f;
     if (do_sample) {
@@ -137,6 +137,14 @@ __device__ inline int sample_pick(float* p, const float* top_v, const int* top_i
                 cum += p[j];
                 if (cum <= 1.f - top_p) keep = j; else break;
             }
+        }
+        // min-p (HF MinPLogitsWarper, after top-p: drop p < min_p * top probability — the ratio survives every renormalisation;
+        // the list is descending, so the survivors are a prefix; entry 0 always stays: min_tokens_to_keep = 1)
+        if (min_p > 0.f) {
+            const float thr = min_p * p[0];
+            int kk = 1;
+            while (kk < keep && p[kk] >= thr) ++kk;
+            keep = kk;
         }
         float z2 = 0.f;
         for (int j = 0; j < keep; ++j) z2 += p[j];
@@ -160,7 +168,7 @@ __global__ __launch_bounds__(NT) void sample_kernel(const float* logits, long ld
                                                     int top_k, float top_p, int do_sample, uint32_t seed,
                                                     const int* step_ptr, uint8_t* finished, int pad_id,
                                                     int eos_id, int eos_id2, int* out_ids, float* out_logp, int* tokens_out,
-                                                    long ldt) {
+                                                    long ldt, float min_p) {
     __shared__ float s_val[NT / 64];
     __shared__ int s_idx[NT / 64];
     __shared__ float top_v[64];
@@ -199,7 +207,7 @@ __global__ __launch_bounds__(NT) void sample_kernel(const float* logits, long ld
     __shared__ float pick_ws[64];
     if (tid == 0)
         sample_pick(pick_ws, top_v, top_i, k, row, temperature, top_p, do_sample, seed, step_ptr ? step_ptr[0] : 0,
-                    finished ? (int)finished[row] : 0, finished, pad_id, eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt);
+                    finished ? (int)finished[row] : 0, finished, pad_id, eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt, min_p);
 }
 
 // stage 2 of the sampler when stage 1 ran: ONE wave per sequence merges the 64 slice lists (each already in the
@@ -210,7 +218,7 @@ __global__ __launch_bounds__(64) void sample_merge_kernel(const float* cand_v, c
                                                           float top_p, int do_sample, uint32_t seed, const int* step_ptr,
                                                           uint8_t* finished, int pad_id, int eos_id, int eos_id2, int* out_ids,
                                                           float* out_logp, int* tokens_out, long ldt, const bf16_t* E,
-                                                          long lde, int H, bf16_t* x, long ldx, float* ss, int nss) {
+                                                          long lde, int H, bf16_t* x, long ldx, float* ss, int nss, float min_p) {
     BRA_DYN_SMEM(smem);                           // values [64][k] | indices [64][k]
     __shared__ float top_v[64];
     __shared__ int top_i[64];
@@ -259,7 +267,7 @@ __global__ __launch_bounds__(64) void sample_merge_kernel(const float* cand_v, c
     __syncthreads();
     if (lane == 0)
         s_choice = sample_pick(pick_ws, top_v, top_i, k, row, temperature, top_p, do_sample, seed, step_v, fin_v, finished, pad_id,
-                               eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt);
+                               eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt, min_p);
     __syncthreads();
     if (!E) return;
     const int tok = s_choice;
@@ -308,18 +316,77 @@ __global__ __launch_bounds__(64) void sample_merge_kernel(const float* cand_v, c
 //            and the (cos | sin) row of that position for the decode attention of the step that follows.
 constexpr int kTileSlices = 8;
 
-__global__ __launch_bounds__(256) void tile_max_kernel(const float* logits, long ldl, int V, float* tmax, long ldm) {
-    const int row = (int)blockIdx.y, tile = (int)blockIdx.x * 256 + (int)threadIdx.x;
-    const int ntiles = (V + 15) / 16;
-    if (tile >= ntiles) return;
-    const float* lr = logits + (long)row * ldl;
+// maximum of the 16-column tile `tile` of one row (the ragged last tile repeats column V - 1)
+__device__ __forceinline__ float tile_max16(const float* lr, int tile, int V) {
     float v[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) { const int c = tile * 16 + j; v[j] = lr[c < V ? c : V - 1]; }
     float m = v[0];
 #pragma unroll
     for (int j = 1; j < 16; ++j) m = fmaxf(m, v[j]);
-    tmax[(long)row * ldm + tile] = m;
+    return m;
+}
+
+__global__ __launch_bounds__(256) void tile_max_kernel(const float* logits, long ldl, int V, float* tmax, long ldm) {
+    const int row = (int)blockIdx.y, tile = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    const int ntiles = (V + 15) / 16;
+    if (tile >= ntiles) return;
+    tmax[(long)row * ldm + tile] = tile_max16(logits + (long)row * ldl, tile, V);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Logits processors in front of the sampler, in place on the fp32 logits the lm_head left (HF: RepetitionPenaltyLogitsProcessor,
+// then MinNewTokensLengthLogitsProcessor — TF:generation/logits_process.py; both run before the warpers the samplers implement).
+// One workgroup per row; `hist` [B, >= t] int32 = the tokens of steps 0 .. t-1 (generated tokens only: with `inputs_embeds` HF
+// has no prompt ids to penalise).
+//   repetition penalty   l < 0 ? l * penalty : l / penalty for every DISTINCT id of the history, once however often it occurs:
+//                        read - barrier - write.  Every history entry first reads its id's logit into LDS; after the barrier every
+//                        entry writes f(original).  Duplicates write the same bits, so there is no dedupe state and nothing carried
+//                        from step to step: the launch is the same issued eagerly, replayed from a graph or after a counter reset.
+//   min_new_tokens       while t < min_new_tokens the EOS logits become -inf (as HF writes them; the candidate keys of the
+//                        samplers order -inf below every finite value and exp(-inf) = 0, so the id is outside the support).  The
+//                        penalty pass leaves a banned id alone: one writer per address.
+//   tile maxima          after a second barrier every touched 16-column tile is RECOMPUTED from its stored logits (the penalty can
+//                        lower a tile's maximum) with the expression of tile_max_kernel.
+// Rows whose `finished` flag is set are skipped (they emit pad whatever the logits say).
+constexpr int kHistMax = 8192;                    // history entries staged in LDS (32 KB)
+
+__global__ __launch_bounds__(256) void logits_process_kernel(float* logits, long ldl, int V, const int* hist, long ldh, int hist_cols,
+                                                             const int* step_ptr, int step_arg, float penalty, int min_new,
+                                                             int eos_id, int eos_id2, const uint8_t* finished, float* tmax, long ldm) {
+    __shared__ float s_orig[kHistMax];
+    const int row = (int)blockIdx.x, tid = (int)threadIdx.x;
+    if (finished && finished[row]) return;        // (uniform over the workgroup: nobody reaches a barrier)
+    int t = step_ptr ? step_ptr[0] : step_arg;
+    t = t < 0 ? 0 : (t > hist_cols ? hist_cols : t);          // never past the history the caller handed in
+    int n = penalty != 1.f ? t : 0;
+    n = n > kHistMax ? kHistMax : n;              // (the entry point refuses what could exceed the staging)
+    float* lr = logits + (long)row * ldl;
+    const int* hr = hist + (long)row * ldh;
+    const bool ban = t < min_new;
+    const int ban1 = (ban && eos_id >= 0 && eos_id < V) ? eos_id : -1, ban2 = (ban && eos_id2 >= 0 && eos_id2 < V) ? eos_id2 : -1;
+    for (int j = tid; j < n; j += 256) {
+        const int id = hr[j];
+        s_orig[j] = (id >= 0 && id < V) ? lr[id] : 0.f;
+    }
+    __syncthreads();
+    for (int j = tid; j < n; j += 256) {
+        const int id = hr[j];
+        if (id < 0 || id >= V || id == ban1 || id == ban2) continue;
+        const float l = s_orig[j];
+        lr[id] = l < 0.f ? l * penalty : l / penalty;
+    }
+    if (tid == 0 && ban1 >= 0) lr[ban1] = -INFINITY;
+    if (tid == 1 && ban2 >= 0) lr[ban2] = -INFINITY;
+    if (!tmax) return;
+    __syncthreads();
+    float* tr = tmax + (long)row * ldm;
+    for (int j = tid; j < n; j += 256) {
+        const int id = hr[j];
+        if (id >= 0 && id < V) tr[id >> 4] = tile_max16(lr, id >> 4, V);
+    }
+    if (tid == 0 && ban1 >= 0) tr[ban1 >> 4] = tile_max16(lr, ban1 >> 4, V);
+    if (tid == 1 && ban2 >= 0) tr[ban2 >> 4] = tile_max16(lr, ban2 >> 4, V);
 }
 
 // NL = list entries per lane in stage 2a (nsl * k <= 64 * NL), NU = gathered logits per lane (16 k <= 64 * NU)
@@ -330,7 +397,7 @@ __global__ __launch_bounds__(64) void sample_tiles_kernel(const float* logits, l
                                                           int eos_id2, int* out_ids, float* out_logp, int* tokens_out, long ldt,
                                                           const bf16_t* E, long lde, int H, bf16_t* x, long ldx, float* ss, int nss,
                                                           const int* pos0, int* pos_out, const float* cosT, const float* sinT, int hd,
-                                                          float* rope_rows) {
+                                                          float* rope_rows, float min_p) {
     __shared__ float sv[kTileSlices * 64];
     __shared__ int si[kTileSlices * 64];
     __shared__ int tsel[64];
@@ -430,7 +497,7 @@ __global__ __launch_bounds__(64) void sample_tiles_kernel(const float* logits, l
     __syncthreads();
     if (lane == 0)
         s_choice = sample_pick(pick_ws, top_v, top_i, k, row, temperature, top_p, do_sample, seed, step_v, fin_v, finished, pad_id,
-                               eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt);
+                               eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt, min_p);
     __syncthreads();
     if (rope_rows) {
         if (hd <= 128) {
@@ -492,7 +559,7 @@ __global__ __launch_bounds__(1024) void sample_tiles_one_kernel(const float* log
                                                                 int eos_id2, int* out_ids, float* out_logp, int* tokens_out, long ldt,
                                                                 const bf16_t* E, long lde, int H, bf16_t* x, long ldx, float* ss, int nss,
                                                                 const int* pos0, int* pos_out, const float* cosT, const float* sinT, int hd,
-                                                                float* rope_rows) {
+                                                                float* rope_rows, float min_p) {
     __shared__ uint64_t lists[64][64];            // [lane-row of the workgroup][rank]
     __shared__ int tsel[64];
     __shared__ float top_v[64];
@@ -609,7 +676,7 @@ __global__ __launch_bounds__(1024) void sample_tiles_one_kernel(const float* log
     int tok = 0;
     if (lane == 0)
         tok = sample_pick(pick_ws, top_v, top_i, k, row, temperature, top_p, do_sample, seed, step_v, fin_v, finished, pad_id,
-                          eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt);
+                          eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt, min_p);
     tok = wave_shfl_i(tok, 0);
     if (rope_rows) {
         if (hd <= 128) {
@@ -679,7 +746,8 @@ __device__ __forceinline__ float blk_sum_f(float v, float* red) {
 template <int NT>
 __global__ __launch_bounds__(NT) void sample_full_kernel(const float* logits, long ldl, int V, float temperature, int top_k, float top_p,
                                                          uint32_t seed, const int* step_ptr, int step_arg, uint8_t* finished, int pad_id,
-                                                         int eos_id, int eos_id2, int* out_ids, float* out_logp, int* tokens_out, long ldt) {
+                                                         int eos_id, int eos_id2, int* out_ids, float* out_logp, int* tokens_out, long ldt,
+                                                         float min_p) {
     __shared__ float red[NT / 64];
     __shared__ float scan[NT];
     const int row = (int)blockIdx.x, tid = (int)threadIdx.x;
@@ -719,11 +787,16 @@ __global__ __launch_bounds__(NT) void sample_full_kernel(const float* logits, lo
         }
         pmin = lo;
     }
-    // ---- multinomial over { ord(l) >= pmin } in index order: thread t owns indices [t per, (t + 1) per)
+    // ---- min-p (MinPLogitsWarper, after top-p): a survivor stays iff its probability is >= min_p x the top probability, i.e.
+    //      e_of(l) >= min_p e_of(m) = min_p — the ratio is the same under every renormalisation; the maximum always stays (1 >= min_p).
+    //      min_p <= 0 makes the test vacuous (e_of >= 0): one threshold form for both
+    const float emin = min_p > 0.f ? min_p : 0.f;
+    auto kept = [&](float l, float e) { return ord_f32(l) >= pmin && e >= emin; };
+    // ---- multinomial over the survivors in index order: thread t owns indices [t per, (t + 1) per)
     const int per = (V + NT - 1) / NT;
     const int j0 = tid * per, j1 = (j0 + per) < V ? (j0 + per) : V;
     float mine = 0.f;
-    for (int j = j0; j < j1; ++j) { const float l = lr[j]; mine += ord_f32(l) >= pmin ? e_of(l) : 0.f; }
+    for (int j = j0; j < j1; ++j) { const float l = lr[j]; const float e = e_of(l); mine += kept(l, e) ? e : 0.f; }
     scan[tid] = mine;
     __syncthreads();
     if (tid == 0) {
@@ -746,8 +819,8 @@ __global__ __launch_bounds__(NT) void sample_full_kernel(const float* logits, lo
         float ep = 1.f, a2 = 0.f;
         for (int j = o0; j < o1; ++j) {
             const float l = lr[j];
-            if (ord_f32(l) >= pmin) {
-                const float e = e_of(l);
+            const float e = e_of(l);
+            if (kept(l, e)) {
                 pick = j; ep = e;
                 if (u < before + a2 + e) break;
                 a2 += e;
@@ -901,9 +974,9 @@ extern "C" int bra_sample_ws_floats(int B, int top_k) {     // workspace size in
 extern "C" int bra_sample_embed(const float* logits, long ldl, int B, int V, float temperature, int top_k, float top_p,
                                 int do_sample, unsigned seed, const int* step_ptr, void* finished, int pad_id, int eos_id, int eos_id2,
                                 int* out_ids, float* out_logp, int* tokens_out, long ldt, void* ws, const void* E, long lde,
-                                int H, void* x, long ldx, float* ss, int nss, void* stream) {
+                                int H, void* x, long ldx, float* ss, int nss, float min_p, void* stream) {
     if (B == 0) return 0;
-    if (!logits || !out_ids || V <= 0 || (do_sample && temperature <= 0.f)) return BRA_ERR_ARG;
+    if (!logits || !out_ids || V <= 0 || (do_sample && temperature <= 0.f) || !(min_p >= 0.f && min_p <= 1.f)) return BRA_ERR_ARG;
     if (!(ws && V <= kSlices * 4096 && V >= 4096)) return BRA_ERR_UNSUPPORTED;
     if (do_sample && (top_k <= 0 || top_k > 64)) return BRA_ERR_UNSUPPORTED;   // the warpers run over <= 64 survivors
     if (E && (!x || H % 8 || lde % 8 || ldx % 8)) return BRA_ERR_ARG;
@@ -916,21 +989,22 @@ extern "C" int bra_sample_embed(const float* logits, long ldl, int B, int V, flo
     if (r) return r;
     BRA_LAUNCH(sample_merge_kernel, dim3(B), dim3(64), (size_t)kSlices * k * 8, stream, (const float*)cv, (const int*)ci, k,
                temperature, top_p, do_sample, (uint32_t)seed, step_ptr, (uint8_t*)finished, pad_id, eos_id, eos_id2, out_ids, out_logp,
-               tokens_out, ldt, (const bf16_t*)E, lde, H, (bf16_t*)x, ldx, ss, nss);
+               tokens_out, ldt, (const bf16_t*)E, lde, H, (bf16_t*)x, ldx, ss, nss, min_p);
     return BRA_LAUNCH_STATUS();
 }
 
 extern "C" int bra_sample(const float* logits, long ldl, int B, int V, float temperature, int top_k, float top_p,
                           int do_sample, unsigned seed, const int* step_ptr, void* finished, int pad_id, int eos_id, int eos_id2,
-                          int* out_ids, float* out_logp, int* tokens_out, long ldt, void* ws, void* stream) {
+                          int* out_ids, float* out_logp, int* tokens_out, long ldt, void* ws, float min_p, void* stream) {
     if (B == 0) return 0;
-    if (!logits || !out_ids || V <= 0 || (do_sample && temperature <= 0.f)) return BRA_ERR_ARG;
+    if (!logits || !out_ids || V <= 0 || (do_sample && temperature <= 0.f) || !(min_p >= 0.f && min_p <= 1.f)) return BRA_ERR_ARG;
     if (do_sample && (top_k <= 0 || top_k > 64)) return BRA_ERR_UNSUPPORTED;       // the warpers run over <= 64 survivors
     if (ws && V <= kSlices * 4096 && V >= 4096)
         return bra_sample_embed(logits, ldl, B, V, temperature, top_k, top_p, do_sample, seed, step_ptr, finished, pad_id,
-                                eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt, ws, nullptr, 0, 0, nullptr, 0, nullptr, 0, stream);
+                                eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt, ws, nullptr, 0, 0, nullptr, 0, nullptr, 0, min_p, stream);
     BRA_LAUNCH((sample_kernel<1024>), dim3(B), dim3(1024), 0, stream, logits, ldl, V, (const int*)nullptr, temperature, top_k, top_p,
-               do_sample, (uint32_t)seed, step_ptr, (uint8_t*)finished, pad_id, eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt);
+               do_sample, (uint32_t)seed, step_ptr, (uint8_t*)finished, pad_id, eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt,
+               min_p);
     return BRA_LAUNCH_STATUS();
 }
 
@@ -952,17 +1026,40 @@ extern "C" int bra_force_token_tiles(float* logits, long ldl, int B, int V, int 
     return BRA_LAUNCH_STATUS();
 }
 
+// repetition penalty + min_new_tokens in place on the logits (and their tile maxima), one launch in front of the sampler — see
+// logits_process_kernel.  hist [B, hist_cols] int32 (pitch ldh): columns 0 .. t-1 are read, t = *step_ptr or `step`, clamped to
+// hist_cols.  No launch where nothing would change (penalty == 1 with min_new_tokens == 0; a host-side t == 0 with nothing to ban).
+// BRA_ERR_UNSUPPORTED: a penalty over a history that may exceed the 8192 entries staged in LDS.
+extern "C" int bra_logits_process(float* logits, long ldl, int B, int V, const int* hist, long ldh, int hist_cols, const int* step_ptr,
+                                  int step, float penalty, int min_new_tokens, int eos_id, int eos_id2, const void* finished,
+                                  float* tmax, long ldm, void* stream) {
+    if (B == 0) return 0;
+    if (!(penalty > 0.f) || min_new_tokens < 0 || hist_cols < 0 || V <= 0) return BRA_ERR_ARG;
+    if (penalty == 1.f && min_new_tokens == 0) return 0;
+    if (!step_ptr && (step < 0 || step > hist_cols)) return BRA_ERR_ARG;
+    if (!step_ptr && step == 0 && min_new_tokens == 0) return 0;
+    if (!logits || (tmax && ldm < (V + 15) / 16)) return BRA_ERR_ARG;
+    if (penalty != 1.f) {
+        if (!hist && hist_cols > 0) return BRA_ERR_ARG;
+        if ((step_ptr ? hist_cols : step) > kHistMax) return BRA_ERR_UNSUPPORTED;
+    }
+    BRA_LAUNCH(logits_process_kernel, dim3(B), dim3(256), 0, stream, logits, ldl, V, hist, ldh, hist_cols, step_ptr, step, penalty,
+               min_new_tokens, eos_id, eos_id2, (const uint8_t*)finished, tmax, ldm);
+    return BRA_LAUNCH_STATUS();
+}
+
 // temperature -> top-k -> top-p -> multinomial for ANY top_k: 0 = no top-k filter (HF's "disabled"), > 64 as given (see
 // sample_full_kernel: exact thresholds by bisection, a slow functional path; 1..64 is what bra_sample / bra_sample_tiles serve).
 // `step_ptr` null: the step index is `step`.
 extern "C" int bra_sample_full(const float* logits, long ldl, int B, int V, float temperature, int top_k, float top_p, unsigned seed,
                                const int* step_ptr, int step, void* finished, int pad_id, int eos_id, int eos_id2, int* out_ids,
-                               float* out_logp, int* tokens_out, long ldt, void* stream) {
+                               float* out_logp, int* tokens_out, long ldt, float min_p, void* stream) {
     if (B == 0) return 0;
-    if (!logits || !out_ids || V <= 0 || temperature <= 0.f || top_k < 0 || !(top_p > 0.f)) return BRA_ERR_ARG;
+    if (!logits || !out_ids || V <= 0 || temperature <= 0.f || top_k < 0 || !(top_p > 0.f) || !(min_p >= 0.f && min_p <= 1.f))
+        return BRA_ERR_ARG;
     if (V >= (1 << 24)) return BRA_ERR_UNSUPPORTED;
     BRA_LAUNCH((sample_full_kernel<1024>), dim3(B), dim3(1024), 0, stream, logits, ldl, V, temperature, top_k, top_p > 1.f ? 1.f : top_p,
-               (uint32_t)seed, step_ptr, step, (uint8_t*)finished, pad_id, eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt);
+               (uint32_t)seed, step_ptr, step, (uint8_t*)finished, pad_id, eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt, min_p);
     return BRA_LAUNCH_STATUS();
 }
 
@@ -994,9 +1091,10 @@ extern "C" int bra_sample_tiles(const float* logits, long ldl, const float* tmax
                                 float top_p, int do_sample, unsigned seed, const int* step_ptr, int step, void* finished, int pad_id,
                                 int eos_id, int eos_id2, int* out_ids, float* out_logp, int* tokens_out, long ldt, void* ws,
                                 const void* E, long lde, int H, void* x, long ldx, float* ss, int nss, const int* pos0, int* pos_out,
-                                const float* cosT, const float* sinT, int hd, float* rope_rows, void* stream) {
+                                const float* cosT, const float* sinT, int hd, float* rope_rows, float min_p, void* stream) {
     if (B == 0) return 0;
-    if (!logits || !tmax || !out_ids || !ws || V <= 0 || (do_sample && temperature <= 0.f)) return BRA_ERR_ARG;
+    if (!logits || !tmax || !out_ids || !ws || V <= 0 || (do_sample && temperature <= 0.f) || !(min_p >= 0.f && min_p <= 1.f))
+        return BRA_ERR_ARG;
     if (do_sample && (top_k <= 0 || top_k > 64)) return BRA_ERR_UNSUPPORTED;
     if (E && (!x || H % 8 || lde % 8 || ldx % 8)) return BRA_ERR_ARG;
     if (rope_rows && (!pos0 || !cosT || !sinT || hd <= 0 || hd % 2)) return BRA_ERR_ARG;
@@ -1010,7 +1108,7 @@ extern "C" int bra_sample_tiles(const float* logits, long ldl, const float* tmax
         BRA_LAUNCH((sample_tiles_one_kernel<EPT_, NU_>), dim3(B), dim3(1024), 0, stream, logits, ldl, V, tmax, ldm, ntiles, k,        \
                    temperature, top_p, do_sample, (uint32_t)seed, step_ptr, step, (uint8_t*)finished, pad_id, eos_id, eos_id2,     \
                    out_ids, out_logp, tokens_out, ldt, (const bf16_t*)E, lde, H, (bf16_t*)x, ldx, ss, nss, pos0, pos_out, cosT,    \
-                   sinT, hd, rope_rows)
+                   sinT, hd, rope_rows, min_p)
         if (ntiles <= 1024 * 10) { if (k <= 20) BRA_ST1(10, 5); else BRA_ST1(10, 16); }
         else { if (k <= 20) BRA_ST1(16, 5); else BRA_ST1(16, 16); }
 #undef BRA_ST1
@@ -1028,7 +1126,7 @@ extern "C" int bra_sample_tiles(const float* logits, long ldl, const float* tmax
     BRA_LAUNCH((sample_tiles_kernel<NL_, NU_>), dim3(B), dim3(64), 0, stream, logits, ldl, V, (const float*)cv, (const int*)ci,  \
                kTileSlices, k, temperature, top_p, do_sample, (uint32_t)seed, step_ptr, step, (uint8_t*)finished, pad_id, eos_id, \
                eos_id2, out_ids, out_logp, tokens_out, ldt, (const bf16_t*)E, lde, H, (bf16_t*)x, ldx, ss, nss, pos0, pos_out,    \
-               cosT, sinT, hd, rope_rows)
+               cosT, sinT, hd, rope_rows, min_p)
     if (k <= 20) BRA_ST(3, 5);
     else BRA_ST(8, 16);
 #undef BRA_ST

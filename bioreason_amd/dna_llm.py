@@ -351,7 +351,9 @@ class DNALLMModel(nn.Module):
         embeds = self._inputs_embeds(input_ids, dna_tokenized, batch_idx_map, dna_alias, dna_enc)
         gc = generation_kwargs.pop("generation_config", None)
         kw = {}
-        for k in ("max_new_tokens", "do_sample", "temperature", "top_k", "top_p", "eos_token_id", "pad_token_id"):
+        # the HF generation keywords this path honours (INTEGRATION.md lists them); any other HF keyword is still ignored
+        for k in ("max_new_tokens", "do_sample", "temperature", "top_k", "top_p", "eos_token_id", "pad_token_id",
+                  "repetition_penalty", "min_new_tokens", "min_p"):
             if gc is not None and getattr(gc, k, None) is not None:
                 kw[k] = getattr(gc, k)
             if k in generation_kwargs and generation_kwargs[k] is not None:
@@ -362,4 +364,7 @@ class DNALLMModel(nn.Module):
                 kw[k] = generation_kwargs[k]
         if not kw.get("do_sample", False):
             kw.pop("temperature", None); kw.pop("top_k", None); kw.pop("top_p", None)
+            mp = kw.pop("min_p", None)      # a warper: HF runs none without do_sample (the two processors above stay)
+            if mp is not None and not 0.0 <= mp <= 1.0:
+                raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {mp!r}")
         return generation.generate(self.text_model, embeds, attention_mask, **kw)

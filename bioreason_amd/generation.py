@@ -642,7 +642,8 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
              force_tokens: Optional[torch.Tensor] = None, native_step: bool = True,
              decode_impl: str = "fused", prompt_alias=None, use_graph: Optional[bool] = None,
              shared_prefix_decode: bool = True, profile: Optional[dict] = None, loop_events: Optional[list] = None,
-             eos_schedule: Optional[torch.Tensor] = None, trace_logits: Optional[list] = None) -> torch.Tensor:
+             eos_schedule: Optional[torch.Tensor] = None, trace_logits: Optional[list] = None,
+             repetition_penalty: float = 1.0, min_new_tokens: int = 0, min_p: Optional[float] = None) -> torch.Tensor:
     """`force_tokens` [B, max_new_tokens] (optional): teacher forcing — the model's own choice is still recorded
     in the output, but the given token is fed back (used to compare decodes position by position).
     `use_graph`: True = sample + decode step + counter update are captured once in a hipGraph and replayed per token
@@ -652,8 +653,26 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
     `eos_token_id` may be an int or a list of up to two ids (HF stops a row on any listed id; Qwen3's generation_config
     lists two); the first one is the pad default.  `eos_schedule` int32 [B] (benchmarks / tests with random-init weights):
     row b is made to draw the first EOS id at step eos_schedule[b].
-    `trace_logits` (tests): a list that receives a copy of the fp32 logits [B, V] after every decode step (eager issue only)."""
+    `trace_logits` (tests): a list that receives a copy of the fp32 logits [B, V] after every decode step (eager issue only), as
+    the step left them — before the processors below.
+    `repetition_penalty`, `min_new_tokens`, `min_p`: HF's RepetitionPenaltyLogitsProcessor, MinNewTokensLengthLogitsProcessor and
+    MinPLogitsWarper in HF's order (penalty -> min length -> temperature -> top-k -> top-p -> min-p).  The penalty runs over the
+    GENERATED tokens only — what HF does for a generate() call with inputs_embeds and no input_ids, as the reference makes it
+    (under `force_tokens`: over the tokens fed back).  The first two are one launch in front of the sampler (ops.logits_process),
+    issued only when one of them is on; min_p lives in the samplers and is ignored when greedy (HF runs no warper then)."""
     _call_kw = dict(locals())                      # every argument of this call, by name (forwarded whole by the row-chunk path)
+    # validation as HF's processors (TF:generation/logits_process.py), plus the bound of the kernel's history staging
+    if isinstance(repetition_penalty, bool) or not isinstance(repetition_penalty, (int, float)) or not repetition_penalty > 0:
+        raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {repetition_penalty!r}")
+    if isinstance(min_new_tokens, bool) or not isinstance(min_new_tokens, int) or min_new_tokens < 0:
+        raise ValueError(f"`min_new_tokens` has to be a non-negative integer, but is {min_new_tokens!r}")
+    if min_p is not None and not 0.0 <= min_p <= 1.0:
+        raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {min_p!r}")
+    if repetition_penalty != 1.0 and max_new_tokens > 8192:
+        raise ValueError("`repetition_penalty` != 1 is supported for max_new_tokens <= 8192 (the history is staged in LDS by "
+                         f"bra_logits_process), but max_new_tokens is {max_new_tokens}")
+    process = repetition_penalty != 1.0 or min_new_tokens > 0
+    min_p_dev = float(min_p) if (do_sample and min_p is not None) else 0.0
     eng = model.ensure_packed()
     B, P, H = inputs_embeds.shape
     dev = inputs_embeds.device
@@ -747,6 +766,11 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
     fuse_adv = use_tiles and rope_args is not None
     pos0 = next_pos.clone() if fuse_adv else None
     counters_at = [0]                       # the step index the device-side counters (step_t, len_t, next_pos) hold
+    # history of the repetition penalty: the [B, max_new_tokens] matrix the sampler fills (columns 0 .. t-1 at step t), or — under
+    # teacher forcing — the tokens fed back, as HF's input_ids would hold them
+    hist = None
+    if process:
+        hist = tokens if force_tokens is None else force_tokens.to(device=dev, dtype=torch.int32).contiguous()
 
     def sample_(t_host: Optional[int] = None):
         """the draw of step t.  `t_host` given: launch-by-launch issue (the index travels as an argument where the kernels take it)"""
@@ -757,14 +781,19 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
             st = t_host if host_step else step_t
             if eos_schedule is not None:
                 ops.force_token_tiles(logits, eos, st, eos_schedule, tmax)
+            if process:                     # (after the schedule, which stands for the model's own logits)
+                ops.logits_process(logits, hist, st, repetition_penalty, min_new_tokens, eos, eos2, fin, tmax)
             ops.sample_tiles(logits, tmax, temperature, top_k, top_p, do_sample, seed, st, fin, pad, cur, None, eos_id=eos,
                              eos_id2=eos2, tokens_out=tokens, ws=sample_ws, embed=emb,
-                             advance=(pos0, next_pos, rope_args[0], rope_args[1], rope_args[2], rope_args[3]) if host_step else None)
+                             advance=(pos0, next_pos, rope_args[0], rope_args[1], rope_args[2], rope_args[3]) if host_step else None,
+                             min_p=min_p_dev)
             return
         if eos_schedule is not None:
             ops.force_token(logits, eos, step_t, eos_schedule)
+        if process:
+            ops.logits_process(logits, hist, step_t, repetition_penalty, min_new_tokens, eos, eos2, fin, None)
         ops.sample(logits, temperature, top_k, top_p, do_sample, seed, step_t, fin, pad,
-                   cur, None, eos_id=eos, eos_id2=eos2, tokens_out=tokens, ws=sample_ws, embed=emb)
+                   cur, None, eos_id=eos, eos_id2=eos2, tokens_out=tokens, ws=sample_ws, embed=emb, min_p=min_p_dev)
 
     def advance_(t_grid: int, exact_t: bool = False):
         """one fused decode step.  Under graph replay the kernels take the step index from step_t / len_t and `t_grid` only sizes
@@ -823,6 +852,8 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
                 else:
                     hid = decode_step(model, cur, cache, kmask, next_pos, P + t)
                 ops.gemm_nt(hid, eng.E, out=logits, out_f32=True)
+                if trace_logits is not None:
+                    trace_logits.append(logits.clone())
                 next_pos.add_(1)
                 step_t.add_(1)
             t += 1

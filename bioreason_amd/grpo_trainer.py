@@ -222,7 +222,9 @@ class DNALLMGRPOTrainer:
             if not callable(f) or isinstance(f, (str, torch.nn.Module)):
                 raise NotImplementedError("reward models are out of scope: reward_funcs must be python callables (reason.py:312-320)")
         self.reward_funcs = reward_funcs
-        # generation settings (:384-391): the warpers are fixed in the reference, not read from args
+        # generation settings (:384-391): the warpers are fixed in the reference, not read from args — args.min_p and
+        # args.repetition_penalty included: the reference never reads them, so they stay ignored here (the controls themselves are
+        # available through bioreason_amd.trainer.GRPOConfig and DNALLMModel.generate)
         self.max_completion_length, self.num_generations = args.max_completion_length, args.num_generations
         eos = processing_class.eos_token_id
         if hasattr(dna_module, "get_eos_token_id"):

@@ -536,9 +536,9 @@ def colsum(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
 
 # --------------------------------------------------------------------------- GRPO / optimiser
 def sample(logits, temperature, top_k, top_p, do_sample, seed, step_t, finished, pad_id, out_ids, out_logp=None,
-           eos_id=-1, tokens_out=None, ws=None, embed=None, eos_id2=-1):
+           eos_id=-1, tokens_out=None, ws=None, embed=None, eos_id2=-1, min_p: float = 0.0):
     """`embed` = (E [V, H], x [B, H], ss [8 | 16 | 32, nss] or None): the drawing wave also writes x[b] = E[token] and the RMSNorm
-    statistic of that row (two-stage path only: V >= 4096)."""
+    statistic of that row (two-stage path only: V >= 4096).  `min_p` (0 = off): HF's MinPLogitsWarper after top-p."""
     B, V = logits.shape
     if do_sample and not (1 <= top_k <= 64):
         # HF's top_k = 0 ("disabled") or more than 64 survivors: the general kernel (exact thresholds by bisection; slow — see
@@ -546,7 +546,7 @@ def sample(logits, temperature, top_k, top_p, do_sample, seed, step_t, finished,
         if embed is not None:
             raise NotImplementedError("the fused embedding gather needs 1 <= top_k <= 64 (callers fall back to the unfused step)")
         return sample_full(logits, temperature, top_k, top_p, seed, step_t, finished, pad_id, out_ids, out_logp, eos_id=eos_id,
-                           eos_id2=eos_id2, tokens_out=tokens_out)
+                           eos_id2=eos_id2, tokens_out=tokens_out, min_p=min_p)
     if ws is None and V >= 4096:
         k = min(top_k, 64) if top_k > 0 else 64
         ws = torch.empty((2 * B * 64 * k,), dtype=torch.float32, device=logits.device)
@@ -555,21 +555,21 @@ def sample(logits, temperature, top_k, top_p, do_sample, seed, step_t, finished,
         E, x, ss = embed
         get_lib().call("bra_sample_embed", logits, _ld(logits), B, V, temperature, top_k, top_p, int(do_sample),
                        seed & 0xFFFFFFFF, step_t, finished, pad_id, eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt, ws, E, _ld(E),
-                       E.shape[1], x, _ld(x), ss, ss.shape[-1] if ss is not None else 0, current_stream(logits))
+                       E.shape[1], x, _ld(x), ss, ss.shape[-1] if ss is not None else 0, float(min_p), current_stream(logits))
         return out_ids
     get_lib().call("bra_sample", logits, _ld(logits), B, V, temperature, top_k, top_p, int(do_sample), seed & 0xFFFFFFFF,
-                   step_t, finished, pad_id, eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt, ws, current_stream(logits))
+                   step_t, finished, pad_id, eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt, ws, float(min_p), current_stream(logits))
     return out_ids
 
 
 def sample_full(logits, temperature, top_k, top_p, seed, step, finished, pad_id, out_ids, out_logp=None, eos_id=-1, eos_id2=-1,
-                tokens_out=None):
+                tokens_out=None, min_p: float = 0.0):
     """temperature -> top-k -> top-p -> multinomial for ANY top_k >= 0 (0: HF's 'disabled'); `step`: device int32 [1], python int or None"""
     B, V = logits.shape
     ldt = tokens_out.stride(0) if tokens_out is not None else 0
     step_ptr, step_i = (step, 0) if isinstance(step, torch.Tensor) else (None, int(step or 0))
     get_lib().call("bra_sample_full", logits, _ld(logits), B, V, temperature, max(int(top_k), 0), top_p, seed & 0xFFFFFFFF, step_ptr, step_i,
-                   finished, pad_id, eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt, current_stream(logits))
+                   finished, pad_id, eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt, float(min_p), current_stream(logits))
     return out_ids
 
 
@@ -583,7 +583,7 @@ def tile_max(logits: torch.Tensor, tmax: Optional[torch.Tensor] = None) -> torch
 
 
 def sample_tiles(logits, tmax, temperature, top_k, top_p, do_sample, seed, step, finished, pad_id, out_ids, out_logp=None, eos_id=-1,
-                 tokens_out=None, ws=None, embed=None, eos_id2=-1, advance=None):
+                 tokens_out=None, ws=None, embed=None, eos_id2=-1, advance=None, min_p: float = 0.0):
     """`sample` over (logits, tile maxima): same tokens, two light launches.  `step`: a device int32 [1] (replayed loops) or a
     python int (the loop issued launch by launch).  `advance` = (pos0 int32 [B], pos_out int32 [B] or None, cosT, sinT, hd,
     rope_rows fp32 [B, hd]): the drawing wave also leaves pos0 + step and the (cos | sin) row of that position."""
@@ -600,8 +600,22 @@ def sample_tiles(logits, tmax, temperature, top_k, top_p, do_sample, seed, step,
     get_lib().call("bra_sample_tiles", logits, _ld(logits), tmax, _ld(tmax), B, V, temperature, top_k, top_p, int(do_sample),
                    seed & 0xFFFFFFFF, step_ptr, step_i, finished, pad_id, eos_id, eos_id2, out_ids, out_logp, tokens_out, ldt, ws,
                    E, _ld(E) if E is not None else 0, E.shape[1] if E is not None else 0, x, _ld(x) if x is not None else 0, ss,
-                   ss.shape[-1] if ss is not None else 0, pos0, pos_out, cosT, sinT, hd, rows, current_stream(logits))
+                   ss.shape[-1] if ss is not None else 0, pos0, pos_out, cosT, sinT, hd, rows, float(min_p), current_stream(logits))
     return out_ids
+
+
+def logits_process(logits: torch.Tensor, hist: Optional[torch.Tensor], step, penalty: float = 1.0, min_new_tokens: int = 0,
+                   eos_id: int = -1, eos_id2: int = -1, finished: Optional[torch.Tensor] = None, tmax: Optional[torch.Tensor] = None):
+    """HF's repetition penalty, then min_new_tokens, in place on fp32 logits [B, V] (and their tile maxima `tmax`) in front of a
+    sampler.  `hist` int32 [B, >= t]: the tokens of steps 0 .. t-1 (generated tokens only); `step` = t: device int32 [1] or python int.
+    Raises KernelError (BRA_ERR_UNSUPPORTED) for a penalty over a history that may exceed 8192 entries."""
+    B, V = logits.shape
+    assert logits.dtype == torch.float32 and (hist is None or (hist.dtype == torch.int32 and hist.stride(1) == 1 and hist.shape[0] == B))
+    step_ptr, step_i = (step, 0) if isinstance(step, torch.Tensor) else (None, int(step))
+    get_lib().call("bra_logits_process", logits, _ld(logits), B, V, hist, hist.stride(0) if hist is not None else 0,
+                   hist.shape[1] if hist is not None else 0, step_ptr, step_i, float(penalty), int(min_new_tokens), int(eos_id),
+                   int(eos_id2), finished, tmax, _ld(tmax) if tmax is not None else 0, current_stream(logits))
+    return logits
 
 
 def force_token_tiles(logits: torch.Tensor, token: int, step, at: torch.Tensor, tmax: Optional[torch.Tensor]):

@@ -42,6 +42,11 @@ class GRPOConfig:
     temperature: float = 0.6
     top_p: float = 0.95
     top_k: int = 20
+    # rollout-only controls (HF generate keywords, TRL's GRPOConfig fields of the same names): they shape which completions are
+    # SAMPLED.  The policy, old-policy and reference log-probs are those of the unprocessed model, as in TRL — with either one on,
+    # the behaviour policy differs from the policy the ratio is taken against.
+    repetition_penalty: float = 1.0
+    min_p: Optional[float] = None
     beta: float = 0.04
     epsilon: float = 0.2
     epsilon_high: Optional[float] = None
@@ -345,7 +350,8 @@ class GRPOStepRunner(_DataParallelStep):
         # rollout (unwrapped_model.generate, :579-596): only completion ids come back
         completion_ids = m.generate(input_ids=prompt_ids, attention_mask=prompt_mask, **mm,
                                     max_new_tokens=c.max_completion_length, do_sample=True, temperature=c.temperature,
-                                    top_k=c.top_k, top_p=c.top_p, eos_token_id=c.eos_token_id, pad_token_id=c.pad_token_id,
+                                    top_k=c.top_k, top_p=c.top_p, repetition_penalty=c.repetition_penalty, min_p=c.min_p,
+                                    eos_token_id=c.eos_token_id, pad_token_id=c.pad_token_id,
                                     seed=c.seed + 1000003 * self.step_idx + self.rank, return_full_length=sched is None,
                                     prompt_alias=batch.get("prompt_alias"), use_graph=c.rollout_graph,
                                     shared_prefix_decode=c.rollout_shared_prefix, eos_schedule=sched,

@@ -368,10 +368,12 @@ int bra_adamw(float* p, const float* g, float* m, float* v, const void* mask, lo
  * receives the token (the [B, C] completion matrix), step_ptr is a device int so a replayed launch advances.
  * eos_id2: a second stop token (HF accepts a list; Qwen3's generation_config has two), -1 = none.
  * do_sample with top_k outside 1..64 is BRA_ERR_UNSUPPORTED: the temperature / top-p / multinomial stage runs over at
- * most 64 survivors (HF's top_k = 0 "disabled" would need a full-vocabulary sort). */
+ * most 64 survivors (HF's top_k = 0 "disabled" would need a full-vocabulary sort).
+ * min_p (every drawing entry point, 0 = off, [0, 1]): HF's MinPLogitsWarper after top-p — of the survivors, those whose probability
+ * is below min_p x the top probability are dropped (the top one always stays); the draw and out_logp renormalise over the rest. */
 int bra_sample(const float* logits, long ldl, int B, int V, float temperature, int top_k, float top_p,
                int do_sample, unsigned seed, const int* step_ptr, void* finished, int pad_id, int eos_id, int eos_id2,
-               int* out_ids, float* out_logp, int* tokens_out, long ldt, void* ws, void* stream);
+               int* out_ids, float* out_logp, int* tokens_out, long ldt, void* ws, float min_p, void* stream);
 /* ws (optional, bra_sample_ws_floats(B, top_k) 4-byte words): enables the two-stage top-k (64 vocabulary slices
  * per row in parallel, then a merge) instead of one workgroup per row scanning the vocabulary k times */
 int bra_sample_ws_floats(int B, int top_k);
@@ -382,7 +384,7 @@ int bra_sample_ws_floats(int B, int top_k);
 int bra_sample_embed(const float* logits, long ldl, int B, int V, float temperature, int top_k, float top_p, int do_sample,
                      unsigned seed, const int* step_ptr, void* finished, int pad_id, int eos_id, int eos_id2, int* out_ids,
                      float* out_logp, int* tokens_out, long ldt, void* ws, const void* E, long lde, int H, void* x, long ldx,
-                     float* ss, int nss, void* stream);
+                     float* ss, int nss, float min_p, void* stream);
 /* synthetic EOS schedule for benchmarks / tests with random-init weights (SURVEY 8d "straggler run"): logits[b, token]
  * is raised above every other entry when *step_ptr == at[b], so row b draws `token` at that step.  B <= 64. */
 int bra_force_token(float* logits, long ldl, int B, int V, int token, const int* step_ptr, const int* at, void* stream);
@@ -400,16 +402,28 @@ int bra_sample_tiles(const float* logits, long ldl, const float* tmax, long ldm,
                      float top_p, int do_sample, unsigned seed, const int* step_ptr, int step, void* finished, int pad_id,
                      int eos_id, int eos_id2, int* out_ids, float* out_logp, int* tokens_out, long ldt, void* ws,
                      const void* E, long lde, int H, void* x, long ldx, float* ss, int nss, const int* pos0, int* pos_out,
-                     const float* cosT, const float* sinT, int hd, float* rope_rows, void* stream);
+                     const float* cosT, const float* sinT, int hd, float* rope_rows, float min_p, void* stream);
 /* sampling with top_k = 0 (HF: top-k disabled) or top_k > 64: thresholds of TopKLogitsWarper / TopPLogitsWarper found by bisection over
  * the row's logits, multinomial over the survivors (one workgroup per row; exact, ~0.1-0.3 ms per token: a functional path — GRPO's
  * top_k = 20 takes bra_sample_tiles).  Ties of equal logits at the top-p boundary are kept or dropped together. */
 int bra_sample_full(const float* logits, long ldl, int B, int V, float temperature, int top_k, float top_p, unsigned seed,
                     const int* step_ptr, int step, void* finished, int pad_id, int eos_id, int eos_id2, int* out_ids,
-                    float* out_logp, int* tokens_out, long ldt, void* stream);
+                    float* out_logp, int* tokens_out, long ldt, float min_p, void* stream);
 /* bra_force_token that also raises the token's tile maximum; `step_ptr` null: the step index is `step` */
 int bra_force_token_tiles(float* logits, long ldl, int B, int V, int token, const int* step_ptr, int step, const int* at,
                           float* tmax, long ldm, void* stream);
+/* HF's RepetitionPenaltyLogitsProcessor, then MinNewTokensLengthLogitsProcessor, in place on the fp32 logits [B, V] in front of a
+ * sampler (TF:generation/logits_process.py; both precede the warpers).  hist [B, hist_cols] int32, pitch ldh: the tokens of steps
+ * 0 .. t-1 with t = *step_ptr (device int) or `step` when step_ptr is null, clamped to hist_cols — the GENERATED tokens only, which is
+ * what HF penalises when generate() is called with inputs_embeds.  Every distinct id of the history gets l < 0 ? l * penalty :
+ * l / penalty once, however often it occurs (each entry reads its logit, a barrier, each entry writes f(original): no state between
+ * launches).  While t < min_new_tokens the logits of eos_id / eos_id2 (where >= 0) become -inf.  tmax (optional, [B, ldm >=
+ * ceil(V / 16)]): the maximum of every touched 16-column tile is recomputed from the stored logits.  Rows whose finished[b] byte
+ * (optional) is set are left alone.  No launch for penalty == 1 with min_new_tokens == 0, nor for a host-side step 0 with nothing to
+ * ban.  BRA_ERR_UNSUPPORTED: penalty != 1 over more than 8192 history entries (hist_cols with a device step). */
+int bra_logits_process(float* logits, long ldl, int B, int V, const int* hist, long ldh, int hist_cols, const int* step_ptr, int step,
+                       float penalty, int min_new_tokens, int eos_id, int eos_id2, const void* finished, float* tmax, long ldm,
+                       void* stream);
 /* counters of the replayed token loop: pos[0..n) += 1, a[0] += 1, b[0] += 1 (a, b optional); when `rope_rows` is given, also
  * rope_rows[i][0..hd/2) = cosT[pos[i]], [hd/2..hd) = sinT[pos[i]] for the NEW positions (see bra_rope_rows) */
 int bra_advance_counters(int* pos, int n, int* a, int* b, const float* cosT, const float* sinT, int hd, float* rope_rows,
