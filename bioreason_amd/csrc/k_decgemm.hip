@@ -41,7 +41,10 @@ namespace bra {
 // F8 (round 5; FAST only): the packed weights are fp8 e4m3 with one fp32 scale per output row (bra_dec_pack_weights_fp8) — HALF the
 // streamed bytes.  A 16-byte request then carries the lane's fragments of TWO consecutive k-steps (8 + 8 bytes), decoded to bf16 in
 // registers (exact: v_cvt_scalef32_pk_bf16_fp8, 4 instructions per step) in front of the same bf16 MFMAs; the row scale multiplies the
-// K-reduced products next to rstd.  Activations, accumulation and every epilogue are unchanged (W8A16).
+// K-reduced products next to rstd.  Activations, accumulation and every epilogue are unchanged (W8A16).  With WIDE == 1 (9 .. 16 rows,
+// bra_dec_pack_weights_fp8_rows(rows = 16): 16-column tiles for every projection) the accumulation order, the LDS hand-off and the
+// two-pass statistics fold are the bf16 16-row form's; the 16-wave forms (K = 4096, 6144) hold one half-size weight set, one tile per
+// workgroup.
 template <int MODE, int NORM, int ACT, int OUTF32, int NW, int NL, int WIDE = 0, int PK = 0, int FAST = 0, int F8 = 0>
 __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS, DecGemm2Args g0) {
     // everything between kernel entry and the first weight / activation request arrives in SGPRs with the wave (kernel-argument
@@ -56,7 +59,9 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
     static_assert(WIDE != 3 || (!FAST && NORM == 0), "32 rows, multi-round: not the fast form, no folded norm");
     static_assert(!WIDE || (MODE == 0 && NORM != 1), "wide rows: 16-column tiles, statistics applied in the epilogue");
     static_assert(!FAST || (PK && NORM != 1), "fast form: packed weights, folded norm or none");
-    static_assert(!F8 || (FAST && NL % 2 == 0 && NW != 16 && !WIDE), "fp8 weights: fast form, two k-steps per 16-byte request");
+    // (16 rows: the same decode in front of the 16-row form's MFMAs, statistics fold and hand-off — row r of a 16-row launch does not
+    //  depend on M; 16 waves exist in the wide row classes only)
+    static_assert(!F8 || (FAST && NL % 2 == 0 && WIDE <= 1 && (WIDE == 1 || NW != 16)), "fp8 weights: fast form, two k-steps per 16-byte request");
     static_assert(WIDE != 2 || !F8, "32 rows: bf16 weights");
     constexpr int NLW = F8 ? NL / 2 : NL;                               // 16-byte weight requests per lane and tile
     constexpr int NH = W32 ? 2 : 1;                               // 16-row halves of the batch (slab rows [h * NW, (h + 1) * NW))
@@ -196,9 +201,12 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
         // folded norm: wave 0 requests the statistics partials behind its weights — all of them, unconditionally (a load that
         // sits under a uniform `4 i < per` test is issued and awaited one at a time: eight serial round trips on the wave
         // that every other wave then waits for at the first barrier) — and folds them in the shadow of the first tile's MFMAs
-        constexpr int NPASS = WIDE == 1 ? 2 : 1;          // (32 rows: waves 0 .. 3 fold eight rows each — 32 registers instead of 64)
+        // (fp8 weights, 16 rows on 16 waves, 128 registers per lane: waves 0 and 1 fold eight rows each, as the 32-row form's waves
+        //  0 .. 3 do — the same partials in the same order per row, so the same rstd — and nothing spills)
+        constexpr bool FOLD2 = F8 && WIDE == 1 && NW == 16;
+        constexpr int NPASS = (WIDE == 1 && !FOLD2) ? 2 : 1;          // (32 rows: waves 0 .. 3 fold eight rows each — 32 registers instead of 64)
         f32x4 sq[NPASS][8];
-        const int swave = W32 ? 4 : 1, sbase = W32 ? 8 * wave : 0;
+        const int swave = W32 ? 4 : (FOLD2 ? 2 : 1), sbase = (W32 || FOLD2) ? 8 * wave : 0;
         if (NORM == 2 && wave < swave) {
 #pragma unroll
             for (int pass = 0; pass < NPASS; ++pass) {
@@ -596,7 +604,8 @@ static int launch_dg2(const DecGemm2Args& g, bra_stream_t st) {
     (void)fast;
 #define BRA_DG2(NW_, NL_)                                                                                                      \
     do {                                                                                                                       \
-        if constexpr (NORM != 1 && !WIDE && NW_ != 16 && NL_ % 2 == 0) {                                                       \
+        /* fp8 images: <= 8 rows on 4 / 8 waves; 9 .. 16 rows in the forms dg2_waves_and_chunks(wide) reaches with one round */   \
+        if constexpr (NORM != 1 && NL_ % 2 == 0 && (WIDE == 0 ? NW_ != 16 : (WIDE == 1 && (NL_ != 4 || NW_ == 4)))) {          \
             if (g.wscale) {                                                                                                    \
                 if (!fast) return BRA_ERR_UNSUPPORTED;                                                                         \
                 BRA_LAUNCH((dec_gemm2_kernel<MODE, NORM, ACT, OUTF32, NW_, NL_, WIDE, 1, 1, 1>), grid, dim3(NW_ * 64), 0, st, BRA_DG2_HEAD_ARGS(g), g); \
@@ -671,13 +680,23 @@ extern "C" int bra_dec_gemm2_packed(const void* x, long ldx, const float* ss_in,
 // fp8 (e4m3) weights with one fp32 scale per output row (bra_dec_pack_weights_fp8): y = rstd * scale[n] * (x Wq^T) ... — the same
 // epilogues as bra_dec_gemm2_packed.  `norm_folded` != 0: ss_in / nss_in carry the statistics of x and the norm weight was folded
 // into Wq before quantisation.  BRA_ERR_UNSUPPORTED outside the single-register-round shapes (the caller keeps bf16 weights there).
-extern "C" int bra_dec_gemm2_fp8(const void* x, long ldx, const float* ss_in, int nss_in, float eps, const void* Wq, const float* wscale,
-                                 const void* res, long ldres, void* out, long ldo, float* ss_out, int nss_out, int M, int N, int K,
-                                 int act, int out_f32, int norm_folded, void* stream) {
+// `image_rows`: the row class the image was packed for (bra_dec_pack_weights_fp8_rows) — 8 streams against M <= 8, 16 (16-column tiles
+// for every projection) against 9 <= M <= 16; any other pairing is BRA_ERR_UNSUPPORTED.
+extern "C" int bra_dec_gemm2_fp8_rows(const void* x, long ldx, const float* ss_in, int nss_in, float eps, const void* Wq, const float* wscale,
+                                      const void* res, long ldres, void* out, long ldo, float* ss_out, int nss_out, int M, int N, int K,
+                                      int act, int out_f32, int norm_folded, int image_rows, void* stream) {
     if (!Wq || !wscale) return BRA_ERR_ARG;
+    if (image_rows == 16 ? (M < 9 || M > 16) : (image_rows != 8 || M > 8)) return BRA_ERR_UNSUPPORTED;
     // (norm_w only selects the folded-norm form here: its values are never read when the weights carry it)
     return dec_gemm2_any(x, ldx, norm_folded ? ss_in : nullptr, norm_folded ? nss_in : 0, norm_folded ? Wq : nullptr, eps, Wq, K, res, ldres,
                          out, ldo, ss_out, nss_out, M, N, K, act, out_f32, norm_folded ? 3 : 1, nullptr, stream, wscale);
+}
+
+extern "C" int bra_dec_gemm2_fp8(const void* x, long ldx, const float* ss_in, int nss_in, float eps, const void* Wq, const float* wscale,
+                                 const void* res, long ldres, void* out, long ldo, float* ss_out, int nss_out, int M, int N, int K,
+                                 int act, int out_f32, int norm_folded, void* stream) {
+    return bra_dec_gemm2_fp8_rows(x, ldx, ss_in, nss_in, eps, Wq, wscale, res, ldres, out, ldo, ss_out, nss_out, M, N, K, act, out_f32,
+                                  norm_folded, 8, stream);
 }
 
 #ifdef BRA_DEBUG
@@ -694,7 +713,8 @@ static int dec_gemm2_any(const void* x, long ldx, const float* ss_in, int nss_in
                         int nss_out, int M, int N, int K, int act, int out_f32, int packed, void* probe, void* stream,
                         const float* wscale) {
     (void)probe;
-    if (wscale && (M > 8 || !(packed & 1) || (norm_w && !(packed & 2)))) return BRA_ERR_UNSUPPORTED;   // fp8 weights: <= 8 rows, packed, norm folded or absent
+    // fp8 weights: <= 16 rows (the entry point pairs the row class of the image with M), packed, norm folded or absent
+    if (wscale && (M > 16 || !(packed & 1) || (norm_w && !(packed & 2)))) return BRA_ERR_UNSUPPORTED;
     if (M <= 0 || M > 32 || N <= 0 || K <= 0 || K % 32 || ldx % 8 || ldw % 8 || !x || !W || !out) return BRA_ERR_ARG;
     if (act && (N % 16 || out_f32 || res || ss_out)) return BRA_ERR_ARG;
     if (out_f32 && res) return BRA_ERR_ARG;            // (out_f32 with ss_out: per-tile maxima of the logits, 16-column tiles)
@@ -770,18 +790,20 @@ extern "C" int bra_dec_pack_weights_rows(const void* W, long ldw, int N, int K, 
 }
 
 // W [N, K] bf16 (optionally with the input's RMSNorm weight folded in) -> fp8 e4m3 image in bra_dec_gemm2_fp8's fragment order
-// (out_q: N * K bytes) + one fp32 scale per row (out_scale: N floats).  Same tile rule as bra_dec_pack_weights for <= 8 batch rows;
-// BRA_ERR_UNSUPPORTED when the shape is not a whole number of tiles and k-step pairs.
-extern "C" int bra_dec_pack_weights_fp8(const void* W, long ldw, int N, int K, int act, int out_f32, const void* norm_w, void* out_q,
-                                        float* out_scale, void* stream) {
-    if (!W || !out_q || !out_scale || N <= 0 || K <= 0 || ldw % 8) return BRA_ERR_ARG;
-    const bool diag = !act && !out_f32 && K % 64 == 0 && dg2_diag_tiles(N);      // bra_dec_gemm2's rule
+// (out_q: N * K bytes) + one fp32 scale per row (out_scale: N floats).  Same tile rule as bra_dec_pack_weights_rows: `rows` <= 8 the
+// 8-row class, 9 .. 16 the 16-column tile order for every projection (same quantiser: the codes and scales of the two images are
+// equal, only their order differs).  BRA_ERR_UNSUPPORTED when the shape is not a whole number of tiles and k-step pairs.
+extern "C" int bra_dec_pack_weights_fp8_rows(const void* W, long ldw, int N, int K, int act, int out_f32, const void* norm_w, int rows,
+                                             void* out_q, float* out_scale, void* stream) {
+    if (!W || !out_q || !out_scale || N <= 0 || K <= 0 || ldw % 8 || rows <= 0 || rows > 16) return BRA_ERR_ARG;
+    const bool wide = rows > 8;
+    const bool diag = !wide && !act && !out_f32 && K % 64 == 0 && dg2_diag_tiles(N);      // bra_dec_gemm2's rule
     if (N % (diag ? 8 : 16) || K % (diag ? 128 : 64)) return BRA_ERR_UNSUPPORTED;
-    {   // only what bra_dec_gemm2_fp8 streams: K exactly one register round of the (waves, chunks) the launcher picks
+    {   // only what bra_dec_gemm2_fp8_rows streams: K exactly one register round of the (waves, chunks) the launcher picks
         int nw, nl;
         const int nsteps = K / (diag ? 64 : 32);
-        dg2_waves_and_chunks(nsteps, false, nw, nl);
-        if (nsteps != nw * nl || nl % 2 || nw == 16) return BRA_ERR_UNSUPPORTED;
+        dg2_waves_and_chunks(nsteps, wide, nw, nl);
+        if (nsteps != nw * nl || nl % 2 || (!wide && nw == 16)) return BRA_ERR_UNSUPPORTED;
     }
     bra_stream_t st = (bra_stream_t)stream;
     BRA_LAUNCH(dec_rowscale_fp8_kernel, dim3((N + 3) / 4), dim3(256), 0, st, (const bf16_t*)W, ldw, N, K, (const bf16_t*)norm_w, out_scale);
@@ -792,6 +814,11 @@ extern "C" int bra_dec_pack_weights_fp8(const void* W, long ldw, int N, int K, i
     if (diag) BRA_LAUNCH((dec_pack_fp8_kernel<1>), grid, dim3(256), 0, st, (const bf16_t*)W, ldw, N, K, (const bf16_t*)norm_w, out_scale, (unsigned*)out_q);
     else BRA_LAUNCH((dec_pack_fp8_kernel<0>), grid, dim3(256), 0, st, (const bf16_t*)W, ldw, N, K, (const bf16_t*)norm_w, out_scale, (unsigned*)out_q);
     return BRA_LAUNCH_STATUS();
+}
+
+extern "C" int bra_dec_pack_weights_fp8(const void* W, long ldw, int N, int K, int act, int out_f32, const void* norm_w, void* out_q,
+                                        float* out_scale, void* stream) {
+    return bra_dec_pack_weights_fp8_rows(W, ldw, N, K, act, out_f32, norm_w, 8, out_q, out_scale, stream);
 }
 
 // statistics columns of a step whose hidden size is H: the workgroups of an N = H projection (one partial each), as a multiple of 32;

@@ -25,8 +25,9 @@ struct Layer {
     const void* head_packed;                                           // record 0 only: fragment-packed lm_head matrix, or null
     const float* rope_rows;                                            // record 0 only: [B, hd] cos | sin rows of the current positions, or null
     float* head_tmax;                                                  // record 0 only: [B, ceil(V / 16)] maxima of the logits' 16-column tiles (sampler), or null
-    // fp8 rollout weights (bra_dec_pack_weights_fp8; flags bit 3: Wqkv / Wo / Wgu / Wd are e4m3 images, bit 4 (record 0): head_packed is):
-    // one fp32 scale per output row of each projection
+    // fp8 rollout weights (bra_dec_pack_weights_fp8_rows; flags bit 3: Wqkv / Wo / Wgu / Wd are ALL e4m3 images, bit 4 (record 0):
+    // head_packed is, bit 5: projection by projection — one is an e4m3 image if and only if its own sc_* is non-null, the others are
+    // bf16 packed images): one fp32 scale per output row of each projection
     const float *sc_qkv, *sc_o, *sc_gu, *sc_d, *sc_head;
 };
 
@@ -94,10 +95,15 @@ static StepGemms step_gemms(float* ss_ws, int nss, int B, int H, int Nq, int Nqk
 static int sg_begin(const StepGemms& s, const void* x) {
     return s.v2 ? bra_row_sumsq(x, s.H, s.B, s.H, s.ssx, s.nss, s.stream) : 0;
 }
+// is this projection of the layer an e4m3 image?  flags bit 3: all four are; bit 5: the ones whose scale pointer is set
+static bool sg_is_fp8(const Layer& l, const float* sc) { return (l.flags & 8) || ((l.flags & 32) && sc); }
+// row class of the fp8 images a step of B rows streams (bra_dec_gemm2_fp8_rows)
+static int sg_image_rows(const StepGemms& s) { return s.B > 8 ? 16 : 8; }
 static int sg_qkv(const StepGemms& s, const Layer& l, const void* x, void* qkv) {
     const int pk = l.flags & 3;
-    if (s.v2 && (l.flags & 8))
-        return bra_dec_gemm2_fp8(x, s.H, s.ssx, s.nss, s.eps, l.Wqkv, l.sc_qkv, nullptr, 0, qkv, s.Nqkv, nullptr, 0, s.B, s.Nqkv, s.H, 0, 0, 1, s.stream);
+    if (s.v2 && sg_is_fp8(l, l.sc_qkv))
+        return bra_dec_gemm2_fp8_rows(x, s.H, s.ssx, s.nss, s.eps, l.Wqkv, l.sc_qkv, nullptr, 0, qkv, s.Nqkv, nullptr, 0, s.B, s.Nqkv, s.H, 0, 0, 1,
+                                      sg_image_rows(s), s.stream);
     if (s.v2) return bra_dec_gemm2_packed(x, s.H, s.ssx, s.nss, l.ln1, s.eps, l.Wqkv, s.H, nullptr, 0, qkv, s.Nqkv, nullptr, 0, s.B, s.Nqkv, s.H, 0, 0, pk, s.stream);
     if (pk) return BRA_ERR_UNSUPPORTED;
     return bra_dec_gemm(x, s.H, l.ln1, s.eps, l.Wqkv, s.H, nullptr, 0, qkv, s.Nqkv, s.B, s.Nqkv, s.H, 0, 0, s.stream);
@@ -106,15 +112,19 @@ static int sg_qkv(const StepGemms& s, const Layer& l, const void* x, void* qkv) 
 static int sg_tail(const StepGemms& s, const Layer& l, const void* o, void* x, void* h, void* act) {
     int rc;
     const int pk = l.flags & 1;
-    if (s.v2 && (l.flags & 8)) {
-        if ((rc = bra_dec_gemm2_fp8(o, s.Nq, nullptr, 0, 0.f, l.Wo, l.sc_o, x, s.H, h, s.H, s.ssh, s.nss, s.B, s.H, s.Nq, 0, 0, 0, s.stream))) return rc;
-        if ((rc = bra_dec_gemm2_fp8(h, s.H, s.ssh, s.nss, s.eps, l.Wgu, l.sc_gu, nullptr, 0, act, s.F, nullptr, 0, s.B, 2 * s.F, s.H, 1, 0, 1, s.stream))) return rc;
-        return bra_dec_gemm2_fp8(act, s.F, nullptr, 0, 0.f, l.Wd, l.sc_d, h, s.H, x, s.H, s.ssx, s.nss, s.B, s.H, s.F, 0, 0, 0, s.stream);
-    }
-    if (s.v2) {
-        if ((rc = bra_dec_gemm2_packed(o, s.Nq, nullptr, 0, nullptr, 0.f, l.Wo, s.Nq, x, s.H, h, s.H, s.ssh, s.nss, s.B, s.H, s.Nq, 0, 0, pk, s.stream))) return rc;
-        if ((rc = bra_dec_gemm2_packed(h, s.H, s.ssh, s.nss, l.ln2, s.eps, l.Wgu, s.H, nullptr, 0, act, s.F, nullptr, 0, s.B, 2 * s.F, s.H, 1, 0, l.flags & 3, s.stream))) return rc;
-        return bra_dec_gemm2_packed(act, s.F, nullptr, 0, nullptr, 0.f, l.Wd, s.F, h, s.H, x, s.H, s.ssx, s.nss, s.B, s.H, s.F, 0, 0, pk, s.stream);
+    if (s.v2) {     // each projection over its own image: e4m3 (bra_dec_gemm2_fp8_rows) or bf16 packed, in the same step
+        const int ir = sg_image_rows(s);
+        rc = sg_is_fp8(l, l.sc_o)
+                 ? bra_dec_gemm2_fp8_rows(o, s.Nq, nullptr, 0, 0.f, l.Wo, l.sc_o, x, s.H, h, s.H, s.ssh, s.nss, s.B, s.H, s.Nq, 0, 0, 0, ir, s.stream)
+                 : bra_dec_gemm2_packed(o, s.Nq, nullptr, 0, nullptr, 0.f, l.Wo, s.Nq, x, s.H, h, s.H, s.ssh, s.nss, s.B, s.H, s.Nq, 0, 0, pk, s.stream);
+        if (rc) return rc;
+        rc = sg_is_fp8(l, l.sc_gu)
+                 ? bra_dec_gemm2_fp8_rows(h, s.H, s.ssh, s.nss, s.eps, l.Wgu, l.sc_gu, nullptr, 0, act, s.F, nullptr, 0, s.B, 2 * s.F, s.H, 1, 0, 1, ir, s.stream)
+                 : bra_dec_gemm2_packed(h, s.H, s.ssh, s.nss, l.ln2, s.eps, l.Wgu, s.H, nullptr, 0, act, s.F, nullptr, 0, s.B, 2 * s.F, s.H, 1, 0, l.flags & 3, s.stream);
+        if (rc) return rc;
+        return sg_is_fp8(l, l.sc_d)
+                   ? bra_dec_gemm2_fp8_rows(act, s.F, nullptr, 0, 0.f, l.Wd, l.sc_d, h, s.H, x, s.H, s.ssx, s.nss, s.B, s.H, s.F, 0, 0, 0, ir, s.stream)
+                   : bra_dec_gemm2_packed(act, s.F, nullptr, 0, nullptr, 0.f, l.Wd, s.F, h, s.H, x, s.H, s.ssx, s.nss, s.B, s.H, s.F, 0, 0, pk, s.stream);
     }
     if (pk) return BRA_ERR_UNSUPPORTED;
     if ((rc = bra_dec_gemm(o, s.Nq, nullptr, 0.f, l.Wo, s.Nq, x, s.H, h, s.H, s.B, s.H, s.Nq, 0, 0, s.stream))) return rc;
@@ -127,7 +137,8 @@ static int sg_head(const StepGemms& s, const void* x, const void* norm_w, const 
                    float* tmax, const float* sc_head = nullptr) {
     const int nt = (s.V + 15) / 16;
     if (s.v2 && Epacked && sc_head)      // fp8 lm_head image (final norm folded)
-        return bra_dec_gemm2_fp8(x, s.H, s.ssx, s.nss, s.eps, Epacked, sc_head, nullptr, 0, logits, s.V, tmax, tmax ? nt : 0, s.B, s.V, s.H, 0, 1, 1, s.stream);
+        return bra_dec_gemm2_fp8_rows(x, s.H, s.ssx, s.nss, s.eps, Epacked, sc_head, nullptr, 0, logits, s.V, tmax, tmax ? nt : 0, s.B, s.V, s.H, 0, 1, 1,
+                                      sg_image_rows(s), s.stream);
     if (s.v2 && Epacked)
         return bra_dec_gemm2_packed(x, s.H, s.ssx, s.nss, norm_w, s.eps, Epacked, s.H, nullptr, 0, logits, s.V, tmax, tmax ? nt : 0, s.B, s.V, s.H, 0, 1, folded ? 3 : 1, s.stream);
     if (s.v2) return bra_dec_gemm2(x, s.H, s.ssx, s.nss, norm_w, s.eps, E, s.H, nullptr, 0, logits, s.V, tmax, tmax ? nt : 0, s.B, s.V, s.H, 0, 1, s.stream);

@@ -32,6 +32,7 @@ _SWITCHES = {
     "BRA_DEC_GEMM_V1": "0",         # 1: first-generation projections (bra_dec_gemm), as where the hidden size needs > 256 statistics columns
     "BRA_DEC_ATTN": "one",          # both: first-generation shared-prefix attention (bra_dec_attn_both + merge)
     "BRA_DEC_ROWS32": "0",          # 1: 17 .. 32 sequences in one token loop
+    "BRA_FP8_WIDE": "1",            # 0: an fp8 rollout streams bf16 images at 9 .. 16 sequences (as before the 16-row fp8 form)
     "BRA_DEC_PERSIST": "0",         # 1 .. 3: persistent step (debug library), prefetch level 0 .. 2
     "BRA_DEC_PERSIST_STOP": "0",    # its diagnostics (bra_qwen_decode_step_persist: stop_after)
     "BRA_SAMPLE_TILES": "1",        # 0: full-scan sampler
@@ -188,7 +189,8 @@ def rollout_weights(model, rows: int = 8):
     pack = _switch("BRA_DEC_PACK") == "1"
     wide = rows > 8             # 9 .. 32 sequences: every projection is packed for 16-column tiles (ops.dec_pack_weights(rows=16));
     #                             the 32-row projections stream the same image — there is no second copy of the rollout weights
-    fp8 = rollout_fp8_enabled(model) and pack and not wide
+    # fp8 images exist in the 8-row and in the 16-row class (ops.dec_pack_weights_fp8(rows=16); BRA_FP8_WIDE=0: bf16 at 9 .. 16 rows)
+    fp8 = rollout_fp8_enabled(model) and pack and rows <= MAX_DECODE_ROWS and (not wide or _switch("BRA_FP8_WIDE") == "1")
     key = (model._packed_sig, model._lora_enabled, pack, wide, fp8, None if arena is None or arena.params is None else (arena.step_count, arena.params._version))
     cached = getattr(eng, "_rollout", None)
     if cached is not None and cached[0] == key:
@@ -210,27 +212,27 @@ def rollout_weights(model, rows: int = 8):
             # RMSNorm weight of the projection's input multiplied in: the kernel then applies rstd to the reduced products and
             # loads no norm weights / statistics ahead of its MFMAs
             nws = {"Wqkv": L.ln1, "Wgu": L.ln2, "Wo": None, "Wd": None}
-            if fp8:
-                # opt-in fp8 rollout weights (BASELINE config 5): e4m3 + one fp32 scale per output row of the MERGED, norm-folded weight;
-                # a layer whose shapes the fp8 kernel does not take keeps bf16 (all four projections together)
-                q8 = {nm: ops.dec_pack_weights_fp8(rec[nm], act=(nm == "Wgu"), norm_w=nws[nm]) for nm in ("Wqkv", "Wo", "Wgu", "Wd")}
-                if all(v is not None for v in q8.values()):
-                    for nm, (q, sc) in q8.items():
-                        rec[nm + "_q"], rec[nm + "_s"] = q, sc
-                    rec["fp8"] = True
+            names = ("Wqkv", "Wo", "Wgu", "Wd")
+            prows = 16 if wide else 8
+            # opt-in fp8 rollout weights (BASELINE config 5): e4m3 + one fp32 scale per output row of the MERGED, norm-folded weight,
+            # projection by projection: one whose shape the fp8 kernel does not take (K beyond one register round: Qwen3-4B's down
+            # projection) keeps its bf16 packed image and the step streams both kinds (`fp8_proj`: the names that are e4m3)
+            q8 = {nm: ops.dec_pack_weights_fp8(rec[nm], act=(nm == "Wgu"), norm_w=nws[nm], rows=prows) if fp8 else None for nm in names}
+            pk = {nm: ops.dec_pack_weights(rec[nm], act=(nm == "Wgu"), norm_w=nws[nm], rows=prows) for nm in names if q8[nm] is None}
+            if all(v is not None for v in pk.values()):
+                rec.update({nm + "_p": v for nm, v in pk.items()})
+                for nm in names:
+                    if q8[nm] is not None:
+                        rec[nm + "_q"], rec[nm + "_s"] = q8[nm]
+                        rec[nm + "_p"] = rec[nm + "_q"]            # (one pointer set for `_packed_ok` / the descriptor table)
+                rec["fp8_proj"] = tuple(nm for nm in names if q8[nm] is not None)
+                if len(rec["fp8_proj"]) == 4:
+                    rec["fp8"] = True                               # all four
                     if fp8_prefill_enabled() and eng.fp8_supported():
                         # the same quantised weights, row-major, for the prompt pass on the fp8 MFMA path (engine._layer_fwd_fp8):
                         # same rule and rounding as the fragment-ordered image above ([gate; up] rows not interleaved there)
                         rec["rm8"] = {"Wqkv": ops.quant_rows_fp8(rec["Wqkv"], colw=L.ln1), "Wo": ops.quant_rows_fp8(rec["Wo"]),
                                       "Wgu": ops.quant_rows_fp8(wgu, colw=L.ln2), "Wd": ops.quant_rows_fp8(rec["Wd"])}
-                    for nm in ("Wqkv", "Wo", "Wgu", "Wd"):
-                        rec[nm + "_p"] = rec[nm + "_q"]            # (one pointer set for `_packed_ok` / the descriptor table)
-                    out.append(rec)
-                    continue
-            pk = {nm: ops.dec_pack_weights(rec[nm], act=(nm == "Wgu"), norm_w=nws[nm], rows=16 if wide else 8)
-                  for nm in ("Wqkv", "Wo", "Wgu", "Wd")}
-            if all(v is not None for v in pk.values()):
-                rec.update({nm + "_p": v for nm, v in pk.items()})
         out.append(rec)
     eng._rollout = (key, out)
     return out
@@ -242,7 +244,7 @@ def fp8_prefill_enabled() -> bool:
 
 
 def prefill_fp8_weights(model, decode_rows: int):
-    """per-layer row-major e4m3 images of the merged policy weights, or None (bf16 rollout, wide decode, a layer the fp8 kernels refuse)"""
+    """per-layer row-major e4m3 images of the merged policy weights, or None (bf16 rollout, a layer with a projection the fp8 kernels refuse, 9 .. 16 rows under BRA_FP8_WIDE=0)"""
     if not (rollout_fp8_enabled(model) and fp8_prefill_enabled()):
         return None
     rw = rollout_weights(model, rows=decode_rows)
@@ -257,14 +259,23 @@ def rollout_fp8_enabled(model) -> bool:
     return bool(getattr(model, "rollout_fp8", False)) or os.environ.get("BRA_ROLLOUT_FP8") == "1"
 
 
-def packed_head_fp8(model):
-    """fp8 image of the tied lm_head with the final RMSNorm weight folded in -> (q, scale) or None (311 MB instead of 622 at Qwen3-1.7B)"""
+def packed_head_fp8(model, rows: int = 8):
+    """fp8 image of the tied lm_head with the final RMSNorm weight folded in -> (q, scale) or None (311 MB instead of 622 at Qwen3-1.7B).
+    rows: the batch of the loop that streams it.  fp32-output projections use 16-column tiles in both row classes, so the 8-row image
+    serves 9 .. 16 rows too; only a hidden size that the 16-row class alone streams in one round (4096, 6144) gets an image of its own"""
     eng: QwenEngine = model.ensure_packed()
     key = (eng.E.data_ptr(), eng.E._version, tuple(eng.E.shape), eng.norm_w.data_ptr(), eng.norm_w._version)
     cached = getattr(eng, "_head_fp8", None)
     if cached is None or cached[0] != key:
-        eng._head_fp8 = (key, ops.dec_pack_weights_fp8(eng.E, out_f32=True, norm_w=eng.norm_w))
-    return eng._head_fp8[1]
+        cached = eng._head_fp8 = (key, {})
+    imgs = cached[1]
+    if 8 not in imgs:
+        imgs[8] = ops.dec_pack_weights_fp8(eng.E, out_f32=True, norm_w=eng.norm_w)
+    if rows <= 8 or imgs[8] is not None:
+        return imgs[8]
+    if 16 not in imgs:
+        imgs[16] = ops.dec_pack_weights_fp8(eng.E, out_f32=True, norm_w=eng.norm_w, rows=16)
+    return imgs[16]
 
 
 def packed_head(model):
@@ -299,7 +310,8 @@ class _FusedStepState:
             if kp is not None:
                 d.kp, d.vtp = kp[i].data_ptr(), vtp[i].data_ptr()
         if use_packed and (B > 8 or _switch("BRA_DEC_PACK_HEAD") == "1"):      # (above 8 rows only the packed head streams)
-            h8 = packed_head_fp8(model) if (B <= 8 and all(R.get("fp8") for R in self.rw)) else None
+            # (fp32-output projections use 16-column tiles in both row classes: one fp8 image of the head serves 1 .. 16 rows)
+            h8 = packed_head_fp8(model, rows=B) if (B <= MAX_DECODE_ROWS and all(R.get("fp8_proj") for R in self.rw)) else None
             if h8 is not None:
                 self.head_p, self.head_s = h8
                 arr[0].head_packed, arr[0].sc_head = self.head_p.data_ptr(), self.head_s.data_ptr()
@@ -387,7 +399,7 @@ class SharedDecodeState(_FusedStepState):
         if mode != "0" and not getattr(get_lib(), "debug", False):
             raise RuntimeError("BRA_DEC_PERSIST needs the debug library (the persistent decode step is not part of the product ABI): "
                                "call bioreason_amd._lib.use_debug_library() first (`make -C bioreason_amd/csrc debug`)")
-        if mode != "0" and self.attn_impl == "one" and self.use_packed and B <= 8 and not any(Rw.get("fp8") for Rw in self.rw) and dev.type == "cuda":
+        if mode != "0" and self.attn_impl == "one" and self.use_packed and B <= 8 and not any(Rw.get("fp8_proj") for Rw in self.rw) and dev.type == "cuda":
             tab = torch.tensor([[Rw["Wqkv_p"].data_ptr(), Rw["Wo_p"].data_ptr(), Rw["Wgu_p"].data_ptr(), Rw["Wd_p"].data_ptr(),
                                  L.qn.data_ptr(), L.kn.data_ptr(), self.kp[i].data_ptr(), self.vtp[i].data_ptr(),
                                  self.kc[i].data_ptr(), self.vc[i].data_ptr()] for i, (L, Rw) in enumerate(zip(eng.layers, self.rw))],
@@ -429,9 +441,11 @@ def _set_proj(d, R, use_packed: bool):
     d.Wqkv, d.Wo, d.Wgu, d.Wd = (R["Wqkv" + sfx].data_ptr(), R["Wo" + sfx].data_ptr(), R["Wgu" + sfx].data_ptr(),
                                   R["Wd" + sfx].data_ptr())
     d.flags = 3 if use_packed else 0
-    if use_packed and R.get("fp8"):                   # e4m3 images + row scales (bra_dec_gemm2_fp8)
-        d.flags |= 8
-        d.sc_qkv, d.sc_o, d.sc_gu, d.sc_d = R["Wqkv_s"].data_ptr(), R["Wo_s"].data_ptr(), R["Wgu_s"].data_ptr(), R["Wd_s"].data_ptr()
+    f8 = R.get("fp8_proj", ()) if use_packed else ()
+    if f8:      # e4m3 images + row scales (bra_dec_gemm2_fp8_rows), projection by projection: flags bit 5, a null sc_* = the bf16 packed image
+        d.flags |= 32 | (8 if len(f8) == 4 else 0)
+        for nm, fld in (("Wqkv", "sc_qkv"), ("Wo", "sc_o"), ("Wgu", "sc_gu"), ("Wd", "sc_d")):
+            setattr(d, fld, R[nm + "_s"].data_ptr() if nm in f8 else None)
 
 
 def _packed_ok(B: int, rw) -> bool:
@@ -512,7 +526,7 @@ def _one_loop_ok(model, B: int) -> bool:
     second-generation statistics workspace; anything else (BRA_DEC_PACK = 0, BRA_DEC_GEMM_V1, a shape the packer
     refuses, fp8 rollout weights) keeps the 16-row chunks"""
     eng = model.ensure_packed()
-    if _norm_stat_nss(eng) == 0 or rollout_fp8_enabled(model):      # (fp8 images stream against <= 8 rows: chunks, as before)
+    if _norm_stat_nss(eng) == 0 or rollout_fp8_enabled(model):      # (fp8 images stream against <= 16 rows: chunks of at most 16)
         return False
     # the K of every projection must select a 32-row form the library has (bra_dec_gemm2 returns BRA_ERR_UNSUPPORTED otherwise, and
     # only at launch time): normed inputs (hidden size: qkv, gate/up, lm_head) and plain ones (q width: o; intermediate size: down)

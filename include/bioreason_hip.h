@@ -226,6 +226,17 @@ int bra_dec_pack_weights_fp8(const void* W, long ldw, int N, int K, int act, int
 int bra_dec_gemm2_fp8(const void* x, long ldx, const float* ss_in, int nss_in, float eps, const void* Wq, const float* wscale,
                       const void* res, long ldres, void* out, long ldo, float* ss_out, int nss_out, int M, int N, int K, int act,
                       int out_f32, int norm_folded, void* stream);
+/* The two entry points above are the `rows` = 8 / `image_rows` = 8 cases of these.  bra_dec_pack_weights_fp8_rows(rows = 9 .. 16): the
+ * 16-column tile order for every projection (as bra_dec_pack_weights_rows), same quantiser — the codes and scales equal the 8-row
+ * image's, in another order; BRA_ERR_UNSUPPORTED unless K is one register round of the 16-row forms: K = 512, 1024, 1536, 2048, 2560,
+ * 3072, 4096 or 6144.  bra_dec_gemm2_fp8_rows(image_rows = 16): 9 <= M <= 16 over such an image, every epilogue, norm folded or
+ * absent; row r of its result does not depend on M.  An image_rows / M pairing other than (8, M <= 8) and (16, 9 .. 16) is
+ * BRA_ERR_UNSUPPORTED (an fp32-output projection has the same image in both classes: pass the class that fits M). */
+int bra_dec_pack_weights_fp8_rows(const void* W, long ldw, int N, int K, int act, int out_f32, const void* norm_w, int rows,
+                                  void* out_q, float* out_scale, void* stream);
+int bra_dec_gemm2_fp8_rows(const void* x, long ldx, const float* ss_in, int nss_in, float eps, const void* Wq, const float* wscale,
+                           const void* res, long ldres, void* out, long ldo, float* ss_out, int nss_out, int M, int N, int K, int act,
+                           int out_f32, int norm_folded, int image_rows, void* stream);
 /* gate/up projection with the SwiGLU in the GEMM epilogue (round 6): act [M, F] = bra_swiglu_fwd(bra_gemm_bf16_nt(A, W [2 F, K] = [gate | up]
  * rows (+ the LoRA rank part A2 B2^T))), bit for bit, without the [M, 2 F] intermediate — no-grad passes only (the backward of a training
  * forward needs gate and up).  BRA_ERR_UNSUPPORTED unless K % 64 == 0, K2 % 64 == 0, F % 128 == 0, M > 16 (callers fall back to the two
