@@ -909,6 +909,47 @@ __global__ __launch_bounds__(64) void attn_decode_merge_kernel(DecodeArgs a) {
         for (int e = 0; e < EPL; ++e) a.o[((long)b * a.Hq + hq) * HD + lane * EPL + e] = f2bf(acc[e] * inv);
 }
 
+// The merge for MORE than 256 chunks (past 16 K keys in 64-key chunks, 32 K in bra_attn_decode's 128-key chunks): the four weight
+// registers of the kernel above hold 256 weights and it reads no chunk behind them.  The host launches this one whenever its chunk
+// count — with a device-side t the count of the longest completion — is above 256; it is right for any count.  Two passes over
+// the (max, sum) pairs: the global maximum first, then the weights in rounds of 64, one per lane, and the partial rows of a round
+// accumulated under that round's weights.  Rare and long: nothing is requested ahead.
+template <int HD>
+__global__ __launch_bounds__(64) void attn_decode_merge_many_kernel(DecodeArgs a) {
+    const int lane = lane_id();
+    const int hq = (int)blockIdx.x, b = (int)blockIdx.y;
+    const int nchunk = a.t_ptr ? a.npc + (a.t_ptr[0] + 64) / 64 : a.nchunk;
+    const long base = ((long)b * a.Hq + hq) * nchunk;
+    constexpr int EPL = HD / 64 > 0 ? HD / 64 : 1;
+    const bool dlive = lane * EPL < HD;
+    float m = kNeg;
+    for (int c = lane; c < nchunk; c += 64) m = fmaxf(m, a.part_ml[(base + c) * 2]);
+    m = wave_max<64>(m);
+    float l = 0.f, acc[EPL];
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
+    for (int c0 = 0; c0 < nchunk; c0 += 64) {
+        const int c = c0 + lane;
+        float w = 0.f;
+        if (c < nchunk) {
+            w = exp2f(a.part_ml[(base + c) * 2] - m);
+            l += a.part_ml[(base + c) * 2 + 1] * w;
+        }
+        const int n = nchunk - c0 < 64 ? nchunk - c0 : 64;
+        for (int u = 0; u < n; ++u) {
+            const float wu = wave_shfl(w, u);
+            if (dlive)
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) acc[e] += a.part_o[(base + c0 + u) * HD + lane * EPL + e] * wu;
+        }
+    }
+    l = wave_sum<64>(l);
+    const float inv = l > 0.f ? 1.f / l : 0.f;
+    if (dlive)
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) a.o[((long)b * a.Hq + hq) * HD + lane * EPL + e] = f2bf(acc[e] * inv);
+}
+
 }  // namespace bra
 
 using namespace bra;
@@ -1218,7 +1259,8 @@ extern "C" int bra_attn_decode(const void* q, const void* kc, const void* vc, co
         BRA_LAUNCH((attn_decode_partial_kernel<HD_, G_>), grid, dim3(256), 0, st, a);                 \
         int r = BRA_LAUNCH_STATUS();                                                                  \
         if (r) return r;                                                                              \
-        BRA_LAUNCH((attn_decode_merge_kernel<HD_>), dim3(Hq, B), dim3(64), 0, st, a);                 \
+        if (a.nchunk > 256) BRA_LAUNCH((attn_decode_merge_many_kernel<HD_>), dim3(Hq, B), dim3(64), 0, st, a);   \
+        else BRA_LAUNCH((attn_decode_merge_kernel<HD_>), dim3(Hq, B), dim3(64), 0, st, a);            \
         return BRA_LAUNCH_STATUS();                                                                   \
     }
     BRA_DEC(128, 1) BRA_DEC(128, 2) BRA_DEC(128, 4)
@@ -1235,9 +1277,16 @@ extern "C" int bra_attn_decode_merge(const float* part_o, const float* part_ml, 
     a.part_o = const_cast<float*>(part_o); a.part_ml = const_cast<float*>(part_ml); a.o = (bf16_t*)o;
     a.B = B; a.Hq = Hq; a.hd = hd; a.nchunk = nchunk; a.t_ptr = t_dev; a.npc = npc;
     bra_stream_t st = (bra_stream_t)stream;
+    // `nchunk` is the largest count the launch can meet (with t_dev: that of the longest completion); above 256 the general merge
+    if (hd != 128 && hd != 64 && hd != 32) return BRA_ERR_UNSUPPORTED;
+    if (nchunk > 256) {
+        if (hd == 128) BRA_LAUNCH((attn_decode_merge_many_kernel<128>), dim3(Hq, B), dim3(64), 0, st, a);
+        else if (hd == 64) BRA_LAUNCH((attn_decode_merge_many_kernel<64>), dim3(Hq, B), dim3(64), 0, st, a);
+        else BRA_LAUNCH((attn_decode_merge_many_kernel<32>), dim3(Hq, B), dim3(64), 0, st, a);
+        return BRA_LAUNCH_STATUS();
+    }
     if (hd == 128) BRA_LAUNCH((attn_decode_merge_kernel<128>), dim3(Hq, B), dim3(64), 0, st, a);
     else if (hd == 64) BRA_LAUNCH((attn_decode_merge_kernel<64>), dim3(Hq, B), dim3(64), 0, st, a);
-    else if (hd == 32) BRA_LAUNCH((attn_decode_merge_kernel<32>), dim3(Hq, B), dim3(64), 0, st, a);
-    else return BRA_ERR_UNSUPPORTED;
+    else BRA_LAUNCH((attn_decode_merge_kernel<32>), dim3(Hq, B), dim3(64), 0, st, a);
     return BRA_LAUNCH_STATUS();
 }

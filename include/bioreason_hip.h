@@ -298,6 +298,9 @@ int bra_dec_attn_both(const void* qkv, long ldqkv, const void* qw, const void* k
                       long vt_sh, long vt_sd, const void* pmask, void* kc, void* vc, float* part_o, float* part_ml, int R,
                       int copies, int Hq, int Hkv, int hd, int P, int C, int t, float eps, float scale, const int* t_dev,
                       const float* rope_rows, void* stream);
+/* merge of the chunk partials [B, Hq, n, hd] / [B, Hq, n, 2] into o [B, Hq * hd].  n = nchunk, or with t_dev the device-side count
+ * npc + (t_dev[0] + 64) / 64 — nchunk is then the count of the LONGEST completion (it sizes nothing, but selects the kernel: above
+ * 256 chunks a general two-pass merge runs instead of the register-resident one; any count is merged in full) */
 int bra_attn_decode_merge(const float* part_o, const float* part_ml, void* o, int B, int Hq, int hd, int nchunk,
                           const int* t_dev, int npc, void* stream);
 int bra_qwen_decode_step_fused(const void* layers_host, int L, int B, int H, int Hq, int Hkv, int hd, int F, int Smax,
