@@ -37,8 +37,11 @@ __device__ __forceinline__ void pin_u32x4(u32x4&) {}
 __device__ __forceinline__ void pin_u32x4(u32x4& v) { asm volatile("" : "+v"(v)); }
 __device__ __forceinline__ void pin_u32(uint32_t& v) { asm volatile("" : "+v"(v)); }
 #endif
+// (-0 and +0 are ONE value of the order, as for the float compares of sample_kernel: equal values go by index alone.  A test of
+//  the bits, not `v + 0.0f`: the device build may fold that addition away, signed zeros being no concern of its arithmetic flags)
 __device__ __forceinline__ uint32_t ord_f32(float v) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    const uint32_t b = __builtin_bit_cast(uint32_t, v);
+    const uint32_t u = b == 0x80000000u ? 0u : b;
     return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
 }
 __device__ __forceinline__ float unord_f32(uint32_t o) {
