@@ -44,7 +44,9 @@ namespace bra {
 // K-reduced products next to rstd.  Activations, accumulation and every epilogue are unchanged (W8A16).  With WIDE == 1 (9 .. 16 rows,
 // bra_dec_pack_weights_fp8_rows(rows = 16): 16-column tiles for every projection) the accumulation order, the LDS hand-off and the
 // two-pass statistics fold are the bf16 16-row form's; the 16-wave forms (K = 4096, 6144) hold one half-size weight set, one tile per
-// workgroup.
+// workgroup.  With WIDE == 2 (17 .. 32 rows, the same rows = 16 image) a request still goes out once and feeds both row halves; k-steps per
+// wave, hand-off, the four-wave statistics fold and the scale next to rstd are unchanged per output element, so row r is bit-identical
+// to row r of the 16-row fp8 form.  No multi-round (WIDE == 3) fp8 form: fp8 images exist at single-round K only.
 template <int MODE, int NORM, int ACT, int OUTF32, int NW, int NL, int WIDE = 0, int PK = 0, int FAST = 0, int F8 = 0>
 __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS, DecGemm2Args g0) {
     // everything between kernel entry and the first weight / activation request arrives in SGPRs with the wave (kernel-argument
@@ -61,8 +63,11 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
     static_assert(!FAST || (PK && NORM != 1), "fast form: packed weights, folded norm or none");
     // (16 rows: the same decode in front of the 16-row form's MFMAs, statistics fold and hand-off — row r of a 16-row launch does not
     //  depend on M; 16 waves exist in the wide row classes only)
-    static_assert(!F8 || (FAST && NL % 2 == 0 && WIDE <= 1 && (WIDE == 1 || NW != 16)), "fp8 weights: fast form, two k-steps per 16-byte request");
-    static_assert(WIDE != 2 || !F8, "32 rows: bf16 weights");
+    // (32 rows: every 16-byte request is issued once and feeds both row halves — decoded once where rows 16 .. 31 have registers of
+    //  their own, a second time behind the first chain on 16 waves, where they take the registers of rows 0 .. 15; the folded norm on
+    //  16 waves x 12 chunks does not fit 128 registers, as with bf16 weights)
+    static_assert(!F8 || (FAST && NL % 2 == 0 && WIDE <= 2 && (WIDE >= 1 || NW != 16)), "fp8 weights: fast form, two k-steps per 16-byte request");
+    static_assert(!(F8 && WIDE == 2 && NORM == 2 && NW == 16 && NL == 12), "32 rows, fp8 weights: no folded norm on 16 waves x 12 chunks");
     constexpr int NLW = F8 ? NL / 2 : NL;                               // 16-byte weight requests per lane and tile
     constexpr int NH = W32 ? 2 : 1;                               // 16-row halves of the batch (slab rows [h * NW, (h + 1) * NW))
     // (32 rows x 16 waves: one slab — 64 KiB of LDS would hold two; the single-round form of 16 waves runs one tile per workgroup,
@@ -266,7 +271,19 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
         };
         auto compute = [&](u32x4 (&wc)[NLW], const f32x4& scc, int t, int it) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (F8 != 0) {
+            f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (F8 != 0 && W32 && !X2LATE) {
+                // 32 rows: a fragment is decoded once and multiplied against both row halves; each accumulator sees the k-steps in the
+                // 16-row form's order
+#pragma unroll
+                for (int u = 0; u < NLW; ++u) {
+                    const u32x4 lo = f8x8_to_bf16x8(wc[u].x, wc[u].y), hi = f8x8_to_bf16x8(wc[u].z, wc[u].w);
+                    acc = mfma_16x16x32(lo, x[2 * u], acc);
+                    acc2 = mfma_16x16x32(lo, x2[2 * u], acc2);
+                    acc = mfma_16x16x32(hi, x[2 * u + 1], acc);
+                    acc2 = mfma_16x16x32(hi, x2[2 * u + 1], acc2);
+                }
+            } else if constexpr (F8 != 0) {
 #pragma unroll
                 for (int u = 0; u < NLW; ++u) {
                     acc = mfma_16x16x32(f8x8_to_bf16x8(wc[u].x, wc[u].y), x[2 * u], acc);
@@ -276,8 +293,20 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
 #pragma unroll
                 for (int u = 0; u < NL; ++u) acc = mfma_16x16x32(wc[u], x[u], acc);
             }
-            f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (X2LATE) {
+            if constexpr (F8 != 0 && X2LATE) {
+                // 16 waves, 128 registers per lane: rows 16 .. 31 take the registers of rows 0 .. 15 and the fragments are decoded again
+                // (4 VALU instructions per k-step, behind the weight stream)
+                sched_fence();
+#pragma unroll
+                for (int u = 0; u < NL; ++u) x[u] = ld16(xp2 + so[u]);
+#pragma unroll
+                for (int u = 0; u < NLW; ++u) {
+                    acc2 = mfma_16x16x32(f8x8_to_bf16x8(wc[u].x, wc[u].y), x[2 * u], acc2);
+                    acc2 = mfma_16x16x32(f8x8_to_bf16x8(wc[u].z, wc[u].w), x[2 * u + 1], acc2);
+                }
+            } else if constexpr (F8 != 0) {
+                // (8 and 16 rows: one half; 32 rows: both chains above)
+            } else if constexpr (X2LATE) {
                 sched_fence();
 #pragma unroll
                 for (int u = 0; u < NL; ++u) x[u] = ld16(xp2 + so[u]);
@@ -323,6 +352,10 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
                         const float rsf = rs_lds[16 + em2_row()];
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] *= rsf;
+                    }
+                    if (F8) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] *= scc[r];
                     }
                     const DecGemm2Args g2 = second_half();
                     dg2_epilogue<MODE, ACT, OUTF32, PK>(g2, v, t, lane, it == 0, resv2);
@@ -575,6 +608,19 @@ static bool dg2_rows32_ok(int K, bool normed, bool packed) {
     return nw * nl <= 64;
 }
 
+// 17 .. 32 rows over an e4m3 image (bra_dec_pack_weights_fp8_rows(rows = 16)): the fast form only — K exactly one register round of
+// an even number of chunks, the single-round K of the 16-row fp8 class (512, 1024, 1536, 2048, 2560, 3072, 4096, 6144) — minus the
+// folded norm on 16 waves x 12 chunks, which the bf16 rule above refuses for the same reason.  (launch_dg2<.., WIDE = 2> asks before
+// it dispatches an image with scales; bra_dec_gemm2_fp8_rows32_ok exports the answer.)
+static bool dg2_fp8_rows32_ok(int K, bool normed) {
+    if (K <= 0 || K % 64) return false;
+    const int nsteps = K / 32;
+    int nw, nl;
+    dg2_waves_and_chunks(nsteps, true, nw, nl);
+    if (nsteps != nw * nl || nl % 2 || (nl == 4 && nw != 4)) return false;
+    return !(normed && nw == 16 && nl == 12);
+}
+
 template <int MODE, int NORM, int ACT, int OUTF32, int WIDE = 0>
 static int launch_dg2(const DecGemm2Args& g, bra_stream_t st) {
     constexpr int KS = MODE ? 64 : 32;
@@ -585,6 +631,7 @@ static int launch_dg2(const DecGemm2Args& g, bra_stream_t st) {
     dg2_waves_and_chunks(nsteps, WIDE != 0, nw, nl);
     if (NORM == 2 && (nsteps + nw * nl - 1) / (nw * nl) != 1) return BRA_ERR_UNSUPPORTED;     // folded norm: single-round path only
     if (WIDE == 2 && !dg2_rows32_ok(g.K, NORM == 2, (g.packed & 1) != 0)) return BRA_ERR_UNSUPPORTED;
+    if (WIDE == 2 && g.wscale && !dg2_fp8_rows32_ok(g.K, NORM == 2)) return BRA_ERR_UNSUPPORTED;
     const int ntiles = MODE ? g.N / 8 : (g.N + 15) / 16;
     // one workgroup of 8 waves (two of 4) per CU, looping over the tiles; the 16-wave form takes one tile per workgroup
     const int gmax = nw == 16 ? ntiles : (nw >= 8 ? 256 : 512);
@@ -604,8 +651,10 @@ static int launch_dg2(const DecGemm2Args& g, bra_stream_t st) {
     (void)fast;
 #define BRA_DG2(NW_, NL_)                                                                                                      \
     do {                                                                                                                       \
-        /* fp8 images: <= 8 rows on 4 / 8 waves; 9 .. 16 rows in the forms dg2_waves_and_chunks(wide) reaches with one round */   \
-        if constexpr (NORM != 1 && NL_ % 2 == 0 && (WIDE == 0 ? NW_ != 16 : (WIDE == 1 && (NL_ != 4 || NW_ == 4)))) {          \
+        /* fp8 images: <= 8 rows on 4 / 8 waves; 9 .. 16 rows in the forms dg2_waves_and_chunks(wide) reaches with one round;    \
+           17 .. 32 rows in the same forms but the folded norm on 16 waves x 12 chunks (dg2_fp8_rows32_ok) */                     \
+        if constexpr (NORM != 1 && NL_ % 2 == 0 && (WIDE == 0 ? NW_ != 16 : ((NL_ != 4 || NW_ == 4) &&                         \
+                      (WIDE == 1 || (WIDE == 2 && !(NORM == 2 && NW_ == 16 && NL_ == 12)))))) {                                \
             if (g.wscale) {                                                                                                    \
                 if (!fast) return BRA_ERR_UNSUPPORTED;                                                                         \
                 BRA_LAUNCH((dec_gemm2_kernel<MODE, NORM, ACT, OUTF32, NW_, NL_, WIDE, 1, 1, 1>), grid, dim3(NW_ * 64), 0, st, BRA_DG2_HEAD_ARGS(g), g); \
@@ -681,12 +730,13 @@ extern "C" int bra_dec_gemm2_packed(const void* x, long ldx, const float* ss_in,
 // epilogues as bra_dec_gemm2_packed.  `norm_folded` != 0: ss_in / nss_in carry the statistics of x and the norm weight was folded
 // into Wq before quantisation.  BRA_ERR_UNSUPPORTED outside the single-register-round shapes (the caller keeps bf16 weights there).
 // `image_rows`: the row class the image was packed for (bra_dec_pack_weights_fp8_rows) — 8 streams against M <= 8, 16 (16-column tiles
-// for every projection) against 9 <= M <= 16; any other pairing is BRA_ERR_UNSUPPORTED.
+// for every projection) against 9 <= M <= 16, 32 the SAME rows = 16 image against 17 <= M <= 32 (each request feeds both 16-row halves;
+// where bra_dec_gemm2_fp8_rows32_ok says so); any other pairing is BRA_ERR_UNSUPPORTED.
 extern "C" int bra_dec_gemm2_fp8_rows(const void* x, long ldx, const float* ss_in, int nss_in, float eps, const void* Wq, const float* wscale,
                                       const void* res, long ldres, void* out, long ldo, float* ss_out, int nss_out, int M, int N, int K,
                                       int act, int out_f32, int norm_folded, int image_rows, void* stream) {
     if (!Wq || !wscale) return BRA_ERR_ARG;
-    if (image_rows == 16 ? (M < 9 || M > 16) : (image_rows != 8 || M > 8)) return BRA_ERR_UNSUPPORTED;
+    if (image_rows == 32 ? (M < 17 || M > 32) : (image_rows == 16 ? (M < 9 || M > 16) : (image_rows != 8 || M > 8))) return BRA_ERR_UNSUPPORTED;
     // (norm_w only selects the folded-norm form here: its values are never read when the weights carry it)
     return dec_gemm2_any(x, ldx, norm_folded ? ss_in : nullptr, norm_folded ? nss_in : 0, norm_folded ? Wq : nullptr, eps, Wq, K, res, ldres,
                          out, ldo, ss_out, nss_out, M, N, K, act, out_f32, norm_folded ? 3 : 1, nullptr, stream, wscale);
@@ -713,8 +763,8 @@ static int dec_gemm2_any(const void* x, long ldx, const float* ss_in, int nss_in
                         int nss_out, int M, int N, int K, int act, int out_f32, int packed, void* probe, void* stream,
                         const float* wscale) {
     (void)probe;
-    // fp8 weights: <= 16 rows (the entry point pairs the row class of the image with M), packed, norm folded or absent
-    if (wscale && (M > 16 || !(packed & 1) || (norm_w && !(packed & 2)))) return BRA_ERR_UNSUPPORTED;
+    // fp8 weights: the entry point pairs the row class of the image with M; packed, norm folded or absent
+    if (wscale && (!(packed & 1) || (norm_w && !(packed & 2)))) return BRA_ERR_UNSUPPORTED;
     if (M <= 0 || M > 32 || N <= 0 || K <= 0 || K % 32 || ldx % 8 || ldw % 8 || !x || !W || !out) return BRA_ERR_ARG;
     if (act && (N % 16 || out_f32 || res || ss_out)) return BRA_ERR_ARG;
     if (out_f32 && res) return BRA_ERR_ARG;            // (out_f32 with ss_out: per-tile maxima of the logits, 16-column tiles)
@@ -830,6 +880,7 @@ extern "C" int bra_dec_stat_cols(int H) {
 }
 
 extern "C" int bra_dec_gemm2_rows32_ok(int K, int normed, int packed) { return dg2_rows32_ok(K, normed != 0, packed != 0) ? 1 : 0; }
+extern "C" int bra_dec_gemm2_fp8_rows32_ok(int K, int normed) { return dg2_fp8_rows32_ok(K, normed != 0) ? 1 : 0; }
 
 extern "C" int bra_row_sumsq(const void* x, long ldx, int M, int K, float* ss, int nss, void* stream) {
     if (M <= 0 || M > 32 || K <= 0 || K % 8 || ldx % 8 || !x || !ss || nss < 1) return BRA_ERR_ARG;

@@ -97,8 +97,8 @@ static int sg_begin(const StepGemms& s, const void* x) {
 }
 // is this projection of the layer an e4m3 image?  flags bit 3: all four are; bit 5: the ones whose scale pointer is set
 static bool sg_is_fp8(const Layer& l, const float* sc) { return (l.flags & 8) || ((l.flags & 32) && sc); }
-// row class of the fp8 images a step of B rows streams (bra_dec_gemm2_fp8_rows)
-static int sg_image_rows(const StepGemms& s) { return s.B > 8 ? 16 : 8; }
+// row class of the fp8 images a step of B rows streams (bra_dec_gemm2_fp8_rows; 32: the rows = 16 images against 17 .. 32 rows)
+static int sg_image_rows(const StepGemms& s) { return s.B > 16 ? 32 : (s.B > 8 ? 16 : 8); }
 static int sg_qkv(const StepGemms& s, const Layer& l, const void* x, void* qkv) {
     const int pk = l.flags & 3;
     if (s.v2 && sg_is_fp8(l, l.sc_qkv))

@@ -33,6 +33,7 @@ _SWITCHES = {
     "BRA_DEC_ATTN": "one",          # both: first-generation shared-prefix attention (bra_dec_attn_both + merge)
     "BRA_DEC_ROWS32": "0",          # 1: 17 .. 32 sequences in one token loop
     "BRA_FP8_WIDE": "1",            # 0: an fp8 rollout streams bf16 images at 9 .. 16 sequences (as before the 16-row fp8 form)
+    "BRA_FP8_ROWS32": "1",          # 0: an fp8 rollout of 17+ sequences keeps 16-row chunks under BRA_DEC_ROWS32=1 (no effect without it)
     "BRA_DEC_PERSIST": "0",         # 1 .. 3: persistent step (debug library), prefetch level 0 .. 2
     "BRA_DEC_PERSIST_STOP": "0",    # its diagnostics (bra_qwen_decode_step_persist: stop_after)
     "BRA_SAMPLE_TILES": "1",        # 0: full-scan sampler
@@ -190,8 +191,15 @@ def rollout_weights(model, rows: int = 8):
     wide = rows > 8             # 9 .. 32 sequences: every projection is packed for 16-column tiles (ops.dec_pack_weights(rows=16));
     #                             the 32-row projections stream the same image — there is no second copy of the rollout weights
     # fp8 images exist in the 8-row and in the 16-row class (ops.dec_pack_weights_fp8(rows=16); BRA_FP8_WIDE=0: bf16 at 9 .. 16 rows)
-    fp8 = rollout_fp8_enabled(model) and pack and rows <= MAX_DECODE_ROWS and (not wide or _switch("BRA_FP8_WIDE") == "1")
-    key = (model._packed_sig, model._lora_enabled, pack, wide, fp8, None if arena is None or arena.params is None else (arena.step_count, arena.params._version))
+    # 17 .. 32 rows stream the rows = 16 e4m3 images (image_rows = 32): the SAME set and the same cache entry as at 9 .. 16 rows
+    # (BRA_FP8_ROWS32=0: generate() keeps 16-row chunks and never asks for more rows; asked anyway, the images are bf16)
+    fp8 = rollout_fp8_enabled(model) and pack and rows <= MAX_DECODE_ROWS32 and (not wide or _switch("BRA_FP8_WIDE") == "1") \
+        and (rows <= MAX_DECODE_ROWS or _switch("BRA_FP8_ROWS32") == "1")
+    # ... except where a 16-row image has no 32-row form — the folded norm at a hidden size of 6144: those projections keep their bf16
+    # packed image at 17 .. 32 rows, a set of its own
+    no32 = bool(fp8 and rows > MAX_DECODE_ROWS and fp8_rows32_form_exists(eng.H, False) and not fp8_rows32_form_exists(eng.H, True))
+    key = (model._packed_sig, model._lora_enabled, pack, wide, fp8, no32,
+           None if arena is None or arena.params is None else (arena.step_count, arena.params._version))
     cached = getattr(eng, "_rollout", None)
     if cached is not None and cached[0] == key:
         return cached[1]
@@ -217,7 +225,8 @@ def rollout_weights(model, rows: int = 8):
             # opt-in fp8 rollout weights (BASELINE config 5): e4m3 + one fp32 scale per output row of the MERGED, norm-folded weight,
             # projection by projection: one whose shape the fp8 kernel does not take (K beyond one register round: Qwen3-4B's down
             # projection) keeps its bf16 packed image and the step streams both kinds (`fp8_proj`: the names that are e4m3)
-            q8 = {nm: ops.dec_pack_weights_fp8(rec[nm], act=(nm == "Wgu"), norm_w=nws[nm], rows=prows) if fp8 else None for nm in names}
+            q8 = {nm: ops.dec_pack_weights_fp8(rec[nm], act=(nm == "Wgu"), norm_w=nws[nm], rows=prows)
+                  if fp8 and not (no32 and nws[nm] is not None) else None for nm in names}
             pk = {nm: ops.dec_pack_weights(rec[nm], act=(nm == "Wgu"), norm_w=nws[nm], rows=prows) for nm in names if q8[nm] is None}
             if all(v is not None for v in pk.values()):
                 rec.update({nm + "_p": v for nm, v in pk.items()})
@@ -262,7 +271,8 @@ def rollout_fp8_enabled(model) -> bool:
 def packed_head_fp8(model, rows: int = 8):
     """fp8 image of the tied lm_head with the final RMSNorm weight folded in -> (q, scale) or None (311 MB instead of 622 at Qwen3-1.7B).
     rows: the batch of the loop that streams it.  fp32-output projections use 16-column tiles in both row classes, so the 8-row image
-    serves 9 .. 16 rows too; only a hidden size that the 16-row class alone streams in one round (4096, 6144) gets an image of its own"""
+    serves 9 .. 16 rows too; only a hidden size that the 16-row class alone streams in one round (4096, 6144) gets an image of its own.
+    17 .. 32 rows stream the image of 9 .. 16 rows (bra_dec_gemm2_fp8_rows(image_rows = 32)) where fp8_rows32_form_exists(H, True)"""
     eng: QwenEngine = model.ensure_packed()
     key = (eng.E.data_ptr(), eng.E._version, tuple(eng.E.shape), eng.norm_w.data_ptr(), eng.norm_w._version)
     cached = getattr(eng, "_head_fp8", None)
@@ -311,7 +321,9 @@ class _FusedStepState:
                 d.kp, d.vtp = kp[i].data_ptr(), vtp[i].data_ptr()
         if use_packed and (B > 8 or _switch("BRA_DEC_PACK_HEAD") == "1"):      # (above 8 rows only the packed head streams)
             # (fp32-output projections use 16-column tiles in both row classes: one fp8 image of the head serves 1 .. 16 rows)
-            h8 = packed_head_fp8(model, rows=B) if (B <= MAX_DECODE_ROWS and all(R.get("fp8_proj") for R in self.rw)) else None
+            # (17 .. 32 rows: the same image, streamed with the 32-row class where that form exists for the hidden size)
+            h8_rows = B <= MAX_DECODE_ROWS or fp8_rows32_form_exists(eng.H, True)
+            h8 = packed_head_fp8(model, rows=B) if (h8_rows and all(R.get("fp8_proj") for R in self.rw)) else None
             if h8 is not None:
                 self.head_p, self.head_s = h8
                 arr[0].head_packed, arr[0].sc_head = self.head_p.data_ptr(), self.head_s.data_ptr()
@@ -521,16 +533,29 @@ def rows32_form_exists(K: int, normed: bool, packed: bool = True) -> bool:
     return bool(get_lib()._dll.bra_dec_gemm2_rows32_ok(int(K), int(normed), int(packed)))
 
 
+def fp8_rows32_form_exists(K: int, normed: bool) -> bool:
+    """does bra_dec_gemm2_fp8_rows(image_rows = 32) stream a rows = 16 e4m3 image of this K against 17 .. 32 rows?  The library's own
+    answer (bra_dec_gemm2_fp8_rows32_ok): the single-round K of the 16-row fp8 class, minus the folded norm at K = 6144"""
+    return bool(get_lib()._dll.bra_dec_gemm2_fp8_rows32_ok(int(K), int(normed)))
+
+
 def _one_loop_ok(model, B: int) -> bool:
-    """17 .. 32 rows in ONE token loop: what the 32-row projections need is folded, bf16, fragment-packed rollout weights and the
+    """17 .. 32 rows in ONE token loop: what the 32-row projections need is folded, fragment-packed rollout weights and the
     second-generation statistics workspace; anything else (BRA_DEC_PACK = 0, BRA_DEC_GEMM_V1, a shape the packer
-    refuses, fp8 rollout weights) keeps the 16-row chunks"""
+    refuses, an fp8 rollout under BRA_FP8_ROWS32=0) keeps the 16-row chunks"""
     eng = model.ensure_packed()
-    if _norm_stat_nss(eng) == 0 or rollout_fp8_enabled(model):      # (fp8 images stream against <= 16 rows: chunks of at most 16)
+    fp8 = rollout_fp8_enabled(model)
+    if _norm_stat_nss(eng) == 0 or (fp8 and _switch("BRA_FP8_ROWS32") != "1"):
         return False
     # the K of every projection must select a 32-row form the library has (bra_dec_gemm2 returns BRA_ERR_UNSUPPORTED otherwise, and
-    # only at launch time): normed inputs (hidden size: qkv, gate/up, lm_head) and plain ones (q width: o; intermediate size: down)
-    if not (rows32_form_exists(eng.H, normed=True) and rows32_form_exists(eng.Nq, normed=False) and rows32_form_exists(eng.F, normed=False)):
+    # only at launch time): normed inputs (hidden size: qkv, gate/up, lm_head) and plain ones (q width: o; intermediate size: down).
+    # In an fp8 rollout a projection streams its e4m3 image where the 32-row fp8 form exists and its bf16 packed image otherwise
+    # (rollout_weights), so either form will do; the bf16 answer alone is asked where no e4m3 image is built (BRA_FP8_WIDE=0)
+    f8 = fp8 and _switch("BRA_FP8_WIDE") == "1"
+
+    def form(K, normed):
+        return (f8 and fp8_rows32_form_exists(K, normed)) or rows32_form_exists(K, normed=normed)
+    if not (form(eng.H, True) and form(eng.Nq, False) and form(eng.F, False)):
         return False
     return _packed_ok(B, rollout_weights(model, rows=B))         # (the same wide image a 9 .. 16-row loop builds and caches)
 

@@ -738,7 +738,9 @@ def gemm_fp8_nt(a8: torch.Tensor, sa: torch.Tensor, b8: torch.Tensor, sb: torch.
 def dec_gemm2_fp8(x, Wq, scale, ss_in=None, eps=1e-6, res=None, act=False, out_f32=False, want_ss=False, tile_max=None, image_rows=8):
     """decode-time projection over fp8 weights (bra_dec_gemm2_fp8_rows): y = [rstd] scale[n] (x q^T) (+res | SwiGLU | fp32);
     `ss_in` given = the input's RMSNorm weight was folded into the weights; returns (y, ss_out or None); None when unsupported.
-    image_rows: the `rows` class the image was packed for — 8 streams against M <= 8, 16 against 9 <= M <= 16"""
+    image_rows: the row class of the call — 8: an image packed with rows <= 8 against M <= 8; 16: one packed with rows = 16 against
+    9 <= M <= 16; 32: the same rows = 16 image against 17 <= M <= 32 (every request feeds both 16-row halves; row r equals row r of
+    an image_rows = 16 call bit for bit; None where bra_dec_gemm2_fp8_rows32_ok(K, normed) is 0).  Any other pairing returns None"""
     M, K = x.shape
     N = Wq.shape[0]
     out = torch.empty((M, N // 2 if act else N), dtype=torch.float32 if out_f32 else x.dtype, device=x.device)

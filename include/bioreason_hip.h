@@ -230,8 +230,13 @@ int bra_dec_gemm2_fp8(const void* x, long ldx, const float* ss_in, int nss_in, f
  * 16-column tile order for every projection (as bra_dec_pack_weights_rows), same quantiser — the codes and scales equal the 8-row
  * image's, in another order; BRA_ERR_UNSUPPORTED unless K is one register round of the 16-row forms: K = 512, 1024, 1536, 2048, 2560,
  * 3072, 4096 or 6144.  bra_dec_gemm2_fp8_rows(image_rows = 16): 9 <= M <= 16 over such an image, every epilogue, norm folded or
- * absent; row r of its result does not depend on M.  An image_rows / M pairing other than (8, M <= 8) and (16, 9 .. 16) is
- * BRA_ERR_UNSUPPORTED (an fp32-output projection has the same image in both classes: pass the class that fits M). */
+ * absent; row r of its result does not depend on M.  bra_dec_gemm2_fp8_rows(image_rows = 32): 17 <= M <= 32 over the SAME rows = 16
+ * image (there is no second image, and the packer keeps refusing rows > 16 with BRA_ERR_ARG) — every 16-byte request is issued once
+ * and multiplied against both 16-row halves of the batch, statistics arrays of 32 rows; row r of its result is bit-identical to row r
+ * of an image_rows = 16 call on the same image and inputs.  It exists where bra_dec_gemm2_fp8_rows32_ok(K, normed) says 1: the K
+ * above, minus the folded norm at K = 6144; BRA_ERR_UNSUPPORTED elsewhere (the caller keeps 16-row chunks or a bf16 image).  An
+ * image_rows / M pairing other than (8, M <= 8), (16, 9 .. 16) and (32, 17 .. 32) is BRA_ERR_UNSUPPORTED (an fp32-output projection
+ * has the same image in every class: pass the class that fits M). */
 int bra_dec_pack_weights_fp8_rows(const void* W, long ldw, int N, int K, int act, int out_f32, const void* norm_w, int rows,
                                   void* out_q, float* out_scale, void* stream);
 int bra_dec_gemm2_fp8_rows(const void* x, long ldx, const float* ss_in, int nss_in, float eps, const void* Wq, const float* wscale,
@@ -273,7 +278,7 @@ int bra_dec_pack_weights(const void* W, long ldw, int N, int K, int act, int out
  * x 8 rollouts per GPU) stream the SAME rows = 16 image — each weight fragment is requested once and multiplied against both
  * 16-row halves of the batch — with 32-row statistics arrays (`ss_ws` of the step functions: float [2][32][nss]); row r of
  * such a call is bit-identical to the same row computed by a 9 .. 16-row call.  BRA_ERR_UNSUPPORTED above 16 rows for an
- * unfolded norm, for fp8 images (bra_dec_gemm2_fp8) and, outside the fast form (packed, K exactly one register round), for the
+ * unfolded norm, for fp8 images outside bra_dec_gemm2_fp8_rows(image_rows = 32) and, outside the fast form (packed, K exactly one register round), for the
  * (waves, chunks) forms that cannot hold both row halves in registers — one clamped round above waves x chunks = 64, K beyond
  * one round on 16 waves unless packed in 8 chunks, the folded norm at K = 6144: the caller splits the batch. */
 int bra_dec_pack_weights_rows(const void* W, long ldw, int N, int K, int act, int out_f32, const void* norm_w, int rows, void* out,
@@ -283,6 +288,9 @@ int bra_row_sumsq(const void* x, long ldx, int M, int K, float* ss, int nss, voi
 int bra_dec_stat_cols(int H);
 /* plan: 1 if bra_dec_gemm2 / _packed have a 17 .. 32-row kernel for this K (`normed`: folded norm, `packed`: bit 0), else 0 */
 int bra_dec_gemm2_rows32_ok(int K, int normed, int packed);
+/* plan: 1 if bra_dec_gemm2_fp8_rows(image_rows = 32) has a kernel for this K (`normed`: folded norm), else 0 — the rule the launcher
+ * dispatches by */
+int bra_dec_gemm2_fp8_rows32_ok(int K, int normed);
 /* `t_dev` / `len_dev` (optional device int): when given, the attention kernels read the current length from it and
  * the host-side `cur_len` / `t` only size the grids (pass the maximum); the launch arguments are then identical for
  * every step, so one captured hipGraph replays the whole rollout (HF `_sample` loop, TF:generation/utils.py:2876-2925). */
