@@ -3,6 +3,7 @@
 #pragma once
 #include "bra_device.h"
 #include "bra_gridsync.h"
+#include "bra_api_internal.h"
 
 namespace bra {
 
@@ -169,6 +170,90 @@ __device__ __forceinline__ void dg2_epilogue(const DecGemm2Args& g, float (&v)[4
             else g.ss_out[(long)m * g.nss_out + tile] = ss;
         }
     }
+}
+
+// ---- host side: which dec_gemm2_kernel (k_decgemm.hip) serves which call.  Stated here once: the launcher, the packers, the plan
+// queries (bra_dec_gemm2_rows32_ok, bra_dec_gemm2_fp8_rows32_ok), the step driver (k_decode.hip) and bra_dec_gemm2_form ask.
+
+// row class of a call of M rows: 8 (8- or 16-column tiles), 16 (16-column tiles everywhere: a diagonal tile holds 8 rows), 32 (the
+// 16-row class's tiles and weight image, two row halves per weight fragment)
+constexpr int dg2_row_class(int M) { return M <= 8 ? 8 : (M <= 16 ? 16 : 32); }
+
+// 8-column (diagonal) tiles for this projection?  dg2_diag_tiles and what the call adds
+inline bool dg2_diag(int rows, int N, int K, int act, int out_f32) { return rows <= 8 && !act && !out_f32 && K % 64 == 0 && dg2_diag_tiles(N); }
+
+// waves per workgroup and 16-byte chunks per lane of a projection with `nsteps` k-steps
+constexpr void dg2_waves_and_chunks(int nsteps, bool wide, int& nw, int& nl) {
+    // (wide rows stream K = 6144 of down_proj in 32-deep steps — the 8-row form takes it in 64-deep diagonal steps — so that
+    //  projection runs 16 waves to keep the single register round)
+    nw = (wide && nsteps >= 128) ? 16 : (nsteps >= 64 ? 8 : 4);
+    const int spw = (nsteps + nw - 1) / nw;
+    // (10: K = 2560, Qwen3-4B's hidden size — on 8 waves only; 4- and 16-wave shapes with ten steps per wave take nl = 8 in the
+    //  generic multi-round loop, as before that form existed)
+    nl = (spw >= 12 && spw % 12 == 0) ? 12 : ((spw == 10 && nw == 8) ? 10 : (spw > 4 ? 8 : 4));
+}
+
+// the form: dec_gemm2_kernel's template arguments, in its order (wide: 0 / 1 / 2 = 8 / 16 / 32 rows, 3 = 32 rows in the multi-round loop)
+struct Dg2Form { int mode, norm, act, outf32, nw, nl, wide, pk, fast, f8; };
+
+// every (waves, chunks) dg2_waves_and_chunks returns: 8 and 16 waves have at least 8 steps each, so never (8, 4) or (16, 4)
+constexpr int DG2_SHAPES[8][2] = {{4, 4}, {4, 8}, {4, 12}, {8, 8}, {8, 10}, {8, 12}, {16, 8}, {16, 12}};
+
+// THE list of instantiations: the forms a valid call reaches, nothing else.  What is not here is not compiled, and a call that maps to
+// it is BRA_ERR_UNSUPPORTED.
+constexpr bool dg2_kernel_exists(const Dg2Form& f) {
+    bool shape = false;
+    for (int s = 0; s < 8; ++s) shape = shape || (DG2_SHAPES[s][0] == f.nw && DG2_SHAPES[s][1] == f.nl);
+    if (!shape || (f.act && f.outf32)) return false;
+    if (f.mode && (f.wide || f.act || f.outf32)) return false;     // diagonal tiles: 8 rows, bf16 epilogue (dg2_diag)
+    if (f.nw == 16 && !f.wide) return false;                       // no 16-wave form below 9 rows: 64-deep steps or 8 waves cover their K
+    if (f.wide && f.norm == 1) return false;                       // wide rows: statistics applied in the epilogue (folded norm) or none
+    if (f.norm == 2 && !f.pk) return false;                        // the folded norm lives in a packed image (bra_dec_pack_weights, norm_w)
+    if (f.fast && (!f.pk || f.norm == 1)) return false;            // fast form: packed weights, folded norm or none
+    // fp8 images: two k-steps per 16-byte request, exact K only (the packer writes nothing else): the fast form with an even chunk count
+    if (f.f8 && (!f.fast || f.nl % 2 || f.wide == 3)) return false;
+    // 32 rows, folded norm on 16 waves x 12 chunks — a hidden size of 6144: the statistics fold does not fit 128 registers (bf16 and fp8)
+    if (f.wide == 2 && f.norm == 2 && f.nw == 16 && f.nl == 12) return false;
+    // 32 rows, one round outside the fast form (steps clamped, row-major weights, 64-bit offsets): only where both row halves are held
+    // without scratch — anything else is refused and the caller splits the batch
+    if (f.wide == 2 && !f.fast && f.nw * f.nl > 64) return false;
+    // 32 rows, K beyond one round: a kernel of its own, no folded norm.  dg2_waves_and_chunks leaves one round only in 8 chunks (10 and 12
+    // are picked where they cover K; 24 steps on each of 16 waves is K = 12288); on 16 waves, 128 registers per lane, packed weights only
+    // (Qwen3-4B's down projection)
+    if (f.wide == 3 && (f.fast || f.norm || f.nl != 8 || (f.nw == 16 && !f.pk))) return false;
+    return true;
+}
+
+// a call, as far as the choice of kernel depends on it (`packed`: bit 0 fragment order, bit 1 norm folded; `fp8`: W is an e4m3 image)
+struct Dg2Call { int M, N, K, act, out_f32, normed, packed, fp8; long ldx, ldres; int nss_in, probed; };
+
+// call -> form and workgroups, or BRA_ERR_UNSUPPORTED.  The call's arguments are valid (dec_gemm2_any checks them first).
+inline int dg2_form_of(const Dg2Call& c, Dg2Form& f, int& grid) {
+    const int rows = dg2_row_class(c.M);
+    f.mode = dg2_diag(rows, c.N, c.K, c.act, c.out_f32);
+    f.norm = c.normed ? ((c.packed & 2) ? 2 : 1) : 0;
+    f.act = c.act != 0; f.outf32 = c.out_f32 != 0;
+    const int nsteps = c.K / (f.mode ? 64 : 32);
+    dg2_waves_and_chunks(nsteps, rows > 8, f.nw, f.nl);
+    const bool multi = nsteps > f.nw * f.nl;
+    // (wide rows beyond one register round — Qwen3-4B's down projection, K = 9728 — take the generic multi-round loop like 8 rows;
+    //  only the folded-norm form is tied to the single-round path)
+    if (f.norm == 2 && multi) return BRA_ERR_UNSUPPORTED;
+    f.wide = rows == 8 ? 0 : (rows == 16 ? 1 : (multi ? 3 : 2));
+    f.pk = c.packed & 1;
+    // fast form: see the kernel; everything it assumes is checked here (a probed launch carries stamps: never fast)
+    const long R = rows == 32 ? 32 : 16;
+    const bool fits32 = c.ldx < (1 << 24) && c.ldres < (1 << 24) && R * c.ldx < (1L << 30) && R * c.ldres + c.N < (1L << 30) &&
+                        R * c.nss_in < (1L << 24);
+    f.fast = f.norm != 1 && f.pk && nsteps == f.nw * f.nl && !c.probed && fits32;
+    f.f8 = c.fp8 != 0;
+    if (!dg2_kernel_exists(f)) return BRA_ERR_UNSUPPORTED;
+    // one workgroup of 8 waves (two of 4) per CU, looping over the tiles.  INVARIANT the kernel relies on: 16 waves get one workgroup per
+    // tile — their single-round form reuses x[] for rows 16 .. 31 and has one LDS slab, both wrong for a second tile
+    const int ntiles = f.mode ? c.N / 8 : (c.N + 15) / 16;
+    const int gmax = f.nw == 16 ? ntiles : (f.nw >= 8 ? 256 : 512);
+    grid = ntiles < gmax ? ntiles : gmax;
+    return 0;
 }
 
 }  // namespace bra

@@ -15,6 +15,8 @@
 //     C[j][b] and C[j+8][b+8] are the two K-halves of output (b, j); all 64 lanes stream weights.
 #include "bra_decgemm.h"
 #include "bra_api_internal.h"
+#include <array>
+#include <utility>
 
 namespace bra {
 
@@ -58,21 +60,16 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
     // WIDE == 3: the 32-row form of the multi-round loop alone (K beyond one register round) — a kernel of its own, so that neither
     // path pays for the other's registers
     constexpr bool W32 = WIDE >= 2;
-    static_assert(WIDE != 3 || (!FAST && NORM == 0), "32 rows, multi-round: not the fast form, no folded norm");
-    static_assert(!WIDE || (MODE == 0 && NORM != 1), "wide rows: 16-column tiles, statistics applied in the epilogue");
-    static_assert(!FAST || (PK && NORM != 1), "fast form: packed weights, folded norm or none");
-    // (16 rows: the same decode in front of the 16-row form's MFMAs, statistics fold and hand-off — row r of a 16-row launch does not
-    //  depend on M; 16 waves exist in the wide row classes only)
-    // (32 rows: every 16-byte request is issued once and feeds both row halves — decoded once where rows 16 .. 31 have registers of
-    //  their own, a second time behind the first chain on 16 waves, where they take the registers of rows 0 .. 15; the folded norm on
-    //  16 waves x 12 chunks does not fit 128 registers, as with bf16 weights)
-    static_assert(!F8 || (FAST && NL % 2 == 0 && WIDE <= 2 && (WIDE >= 1 || NW != 16)), "fp8 weights: fast form, two k-steps per 16-byte request");
-    static_assert(!(F8 && WIDE == 2 && NORM == 2 && NW == 16 && NL == 12), "32 rows, fp8 weights: no folded norm on 16 waves x 12 chunks");
+    static_assert(dg2_kernel_exists({MODE, NORM, ACT, OUTF32, NW, NL, WIDE, PK, FAST, F8}), "not a form of bra_decgemm.h's list");
+    // (fp8, 16 rows: the same decode in front of the 16-row form's MFMAs, statistics fold and hand-off — row r of a 16-row launch does
+    //  not depend on M)
+    // (fp8, 32 rows: every 16-byte request is issued once and feeds both row halves — decoded once where rows 16 .. 31 have registers of
+    //  their own, a second time behind the first chain on 16 waves, where they take the registers of rows 0 .. 15)
     constexpr int NLW = F8 ? NL / 2 : NL;                               // 16-byte weight requests per lane and tile
     constexpr int NH = W32 ? 2 : 1;                               // 16-row halves of the batch (slab rows [h * NW, (h + 1) * NW))
     // (32 rows x 16 waves: one slab — 64 KiB of LDS would hold two; the single-round form of 16 waves runs one tile per workgroup,
     //  the multi-round loop pays a second barrier per tile)
-    // INVARIANT (launch_dg2: `gmax = nw == 16 ? ntiles : ..`): the single-round form of 16 waves gets one workgroup per tile — it
+    // INVARIANT (dg2_form_of: `gmax = nw == 16 ? ntiles : ..`): the single-round form of 16 waves gets one workgroup per tile — it
     // reuses x[] for rows 16 .. 31 and has one slab, both wrong for a second tile; the multi-round loop re-reads x and pays the
     // second barrier, so it may walk several tiles
     constexpr int NBUF = (W32 && NW == 16) ? 1 : 2;
@@ -364,7 +361,7 @@ __global__ __launch_bounds__(NW * 64) void dec_gemm2_kernel(BRA_DG2_HEAD_PARAMS,
             if (!FAST && it == 0) dg2_stamp(g, 4);
         };
         if (NW == 16) {                   // 16 waves x 12 chunks: no registers for a second weight set; the host launches one
-            compute(w0, sc0, tile, 0);    // workgroup per tile (launch_dg2)
+            compute(w0, sc0, tile, 0);    // workgroup per tile (dg2_form_of)
             return;
         }
         int it = 0;
@@ -582,125 +579,44 @@ __global__ __launch_bounds__(256) void dec_pack_fp8_kernel(const bf16_t* W, long
     *reinterpret_cast<u32x4*>(out + c * 4) = v;
 }
 
-// waves per workgroup and 16-byte chunks per lane of a projection with `nsteps` k-steps (one rule for the launcher and for the fp8
-// packer, which must refuse what the fp8 kernel cannot stream)
-static void dg2_waves_and_chunks(int nsteps, bool wide, int& nw, int& nl) {
-    nw = (wide && nsteps >= 128) ? 16 : (nsteps >= 64 ? 8 : 4);
-    const int spw = (nsteps + nw - 1) / nw;
-    // (10: K = 2560, Qwen3-4B's hidden size — instantiated for the 8-wave form only; 4- and 16-wave shapes with ten steps per wave
-    //  take nl = 8 in the generic multi-round loop, as before that form existed)
-    nl = (spw >= 12 && spw % 12 == 0) ? 12 : ((spw == 10 && nw == 8) ? 10 : (spw > 4 ? 8 : 4));
+// One slot per value of the form's ten fields: the launcher of the kernel at slot I, or null where dg2_kernel_exists says there is none
+// (nothing is instantiated there).
+using Dg2Launch = int (*)(const DecGemm2Args&, int, bra_stream_t);
+constexpr int DG2_SLOTS = 2 * 3 * 2 * 2 * 8 * 4 * 2 * 2 * 2;
+constexpr Dg2Form dg2_form_at(int i) {
+    Dg2Form f = {};
+    f.f8 = i % 2; i /= 2; f.fast = i % 2; i /= 2; f.pk = i % 2; i /= 2; f.wide = i % 4; i /= 4;
+    f.nw = DG2_SHAPES[i % 8][0]; f.nl = DG2_SHAPES[i % 8][1]; i /= 8;
+    f.outf32 = i % 2; i /= 2; f.act = i % 2; i /= 2; f.norm = i % 3; f.mode = i / 3;
+    return f;
 }
-
-// 17 .. 32 rows over 16-column tiles of 32 k: is there a 32-row kernel for this K?  (launch_dg2<.., WIDE = 2> asks before it
-// dispatches; bra_dec_gemm2_rows32_ok exports the answer to the host, which keeps 16-row chunks where it is no.)
-// The fast form (packed weights, K exactly one register round of the (waves, chunks) above) always, except the folded norm on
-// 16 waves x 12 chunks — a hidden size of 6144: the statistics fold does not fit 128 registers; one clamped round outside the fast
-// form only where both row halves are held without scratch, waves x chunks <= 64; K beyond one round without norm only — packed on
-// 16 waves x 8 chunks (Qwen3-4B's down projection) or on fewer waves, plain layout on fewer than 16 waves.
-static bool dg2_rows32_ok(int K, bool normed, bool packed) {
-    if (K <= 0 || K % 32) return false;
-    const int nsteps = K / 32;
-    int nw, nl;
-    dg2_waves_and_chunks(nsteps, true, nw, nl);
-    if (nsteps > nw * nl) return !normed && (nw < 16 || (nl == 8 && packed));
-    if (packed && nsteps == nw * nl && !(normed && nw == 16 && nl == 12)) return true;
-    return nw * nl <= 64;
+constexpr int dg2_slot(const Dg2Form& f) {        // (of a form that exists)
+    int s = 0;
+    while (DG2_SHAPES[s][0] != f.nw || DG2_SHAPES[s][1] != f.nl) ++s;
+    return (((((((f.mode * 3 + f.norm) * 2 + f.act) * 2 + f.outf32) * 8 + s) * 4 + f.wide) * 2 + f.pk) * 2 + f.fast) * 2 + f.f8;
 }
-
-// 17 .. 32 rows over an e4m3 image (bra_dec_pack_weights_fp8_rows(rows = 16)): the fast form only — K exactly one register round of
-// an even number of chunks, the single-round K of the 16-row fp8 class (512, 1024, 1536, 2048, 2560, 3072, 4096, 6144) — minus the
-// folded norm on 16 waves x 12 chunks, which the bf16 rule above refuses for the same reason.  (launch_dg2<.., WIDE = 2> asks before
-// it dispatches an image with scales; bra_dec_gemm2_fp8_rows32_ok exports the answer.)
-static bool dg2_fp8_rows32_ok(int K, bool normed) {
-    if (K <= 0 || K % 64) return false;
-    const int nsteps = K / 32;
-    int nw, nl;
-    dg2_waves_and_chunks(nsteps, true, nw, nl);
-    if (nsteps != nw * nl || nl % 2 || (nl == 4 && nw != 4)) return false;
-    return !(normed && nw == 16 && nl == 12);
-}
-
-template <int MODE, int NORM, int ACT, int OUTF32, int WIDE = 0>
-static int launch_dg2(const DecGemm2Args& g, bra_stream_t st) {
-    constexpr int KS = MODE ? 64 : 32;
-    const int nsteps = g.K / KS;
-    // (wide rows stream K = 6144 of down_proj in 32-deep steps — the 8-row form takes it in 64-deep diagonal steps — so that
-    //  projection runs 16 waves to keep the single register round)
-    int nw, nl;
-    dg2_waves_and_chunks(nsteps, WIDE != 0, nw, nl);
-    if (NORM == 2 && (nsteps + nw * nl - 1) / (nw * nl) != 1) return BRA_ERR_UNSUPPORTED;     // folded norm: single-round path only
-    if (WIDE == 2 && !dg2_rows32_ok(g.K, NORM == 2, (g.packed & 1) != 0)) return BRA_ERR_UNSUPPORTED;
-    if (WIDE == 2 && g.wscale && !dg2_fp8_rows32_ok(g.K, NORM == 2)) return BRA_ERR_UNSUPPORTED;
-    const int ntiles = MODE ? g.N / 8 : (g.N + 15) / 16;
-    // one workgroup of 8 waves (two of 4) per CU, looping over the tiles; the 16-wave form takes one tile per workgroup
-    const int gmax = nw == 16 ? ntiles : (nw >= 8 ? 256 : 512);
-    const dim3 grid(ntiles < gmax ? ntiles : gmax);
-    // (wide rows beyond one register round — Qwen3-4B's down projection, K = 9728 — take the generic multi-round loop like 8 rows;
-    //  only the folded-norm form, refused above, is tied to the single-round path)
-    // fast form: see the kernel; everything it assumes is checked here
-    constexpr long ROWS = WIDE == 2 ? 32 : 16;
-    const bool fits32 = g.ldx < (1 << 24) && g.ldres < (1 << 24) && ROWS * g.ldx < (1L << 30) && ROWS * g.ldres + g.N < (1L << 30) &&
-                        ROWS * g.nss_in < (1L << 24);
-#ifdef BRA_DEBUG
-    const bool probed = g.probe != nullptr;          // the fast form carries no stamps
-#else
-    const bool probed = false;
-#endif
-    const bool fast = NORM != 1 && (g.packed & 1) && nsteps == nw * nl && !probed && fits32;
-    (void)fast;
-#define BRA_DG2(NW_, NL_)                                                                                                      \
-    do {                                                                                                                       \
-        /* fp8 images: <= 8 rows on 4 / 8 waves; 9 .. 16 rows in the forms dg2_waves_and_chunks(wide) reaches with one round;    \
-           17 .. 32 rows in the same forms but the folded norm on 16 waves x 12 chunks (dg2_fp8_rows32_ok) */                     \
-        if constexpr (NORM != 1 && NL_ % 2 == 0 && (WIDE == 0 ? NW_ != 16 : ((NL_ != 4 || NW_ == 4) &&                         \
-                      (WIDE == 1 || (WIDE == 2 && !(NORM == 2 && NW_ == 16 && NL_ == 12)))))) {                                \
-            if (g.wscale) {                                                                                                    \
-                if (!fast) return BRA_ERR_UNSUPPORTED;                                                                         \
-                BRA_LAUNCH((dec_gemm2_kernel<MODE, NORM, ACT, OUTF32, NW_, NL_, WIDE, 1, 1, 1>), grid, dim3(NW_ * 64), 0, st, BRA_DG2_HEAD_ARGS(g), g); \
-                break;                                                                                                         \
-            }                                                                                                                  \
-        }                                                                                                                      \
-        if (g.wscale) return BRA_ERR_UNSUPPORTED;                                                                              \
-        /* (32 rows, folded norm on 16 waves x 12 chunks — a hidden size of 6144: the statistics fold does not fit 128 registers) */ \
-        if constexpr (NORM != 1 && !(WIDE == 2 && NORM == 2 && NW_ == 16 && NL_ == 12)) {                                      \
-            if (fast) {                                                                                                        \
-                BRA_LAUNCH((dec_gemm2_kernel<MODE, NORM, ACT, OUTF32, NW_, NL_, WIDE, 1, 1>), grid, dim3(NW_ * 64), 0, st, BRA_DG2_HEAD_ARGS(g), g); \
-                break;                                                                                                         \
-            }                                                                                                                  \
-        }                                                                                                                      \
-        if constexpr (WIDE == 2) {                                                                                             \
-            /* 32 rows outside the fast form: K beyond one register round runs the multi-round loop as its own kernel (WIDE == 3);  \
-               one clamped round only in the (waves, chunks) forms that hold both row halves without scratch — NW * NL <= 64 —     \
-               anything else is refused and the caller splits the batch */                                                          \
-            if (nsteps > NW_ * NL_) {                                                                                          \
-                /* (16 waves, 128 registers per lane: packed weights in 8 chunks — Qwen3-4B's down projection — and nothing else) */ \
-                if constexpr (NORM == 0 && (NW_ < 16 || NL_ == 8)) {                                                           \
-                    if (g.packed & 1) {                                                                                        \
-                        BRA_LAUNCH((dec_gemm2_kernel<MODE, NORM, ACT, OUTF32, NW_, NL_, 3, 1>), grid, dim3(NW_ * 64), 0, st, BRA_DG2_HEAD_ARGS(g), g); \
-                        break;                                                                                                 \
-                    }                                                                                                          \
-                    if constexpr (NW_ < 16) {                                                                                  \
-                        BRA_LAUNCH((dec_gemm2_kernel<MODE, NORM, ACT, OUTF32, NW_, NL_, 3, 0>), grid, dim3(NW_ * 64), 0, st, BRA_DG2_HEAD_ARGS(g), g); \
-                        break;                                                                                                 \
-                    }                                                                                                          \
-                }                                                                                                              \
-                return BRA_ERR_UNSUPPORTED;                                                                                    \
-            }                                                                                                                  \
-            if constexpr (NW_ * NL_ > 64) return BRA_ERR_UNSUPPORTED;                                                          \
-        }                                                                                                                      \
-        if constexpr (!(WIDE == 2 && NW_ * NL_ > 64)) {                                                                        \
-            if (g.packed & 1) BRA_LAUNCH((dec_gemm2_kernel<MODE, NORM, ACT, OUTF32, NW_, NL_, WIDE, 1>), grid, dim3(NW_ * 64), 0, st, BRA_DG2_HEAD_ARGS(g), g); \
-            else BRA_LAUNCH((dec_gemm2_kernel<MODE, NORM, ACT, OUTF32, NW_, NL_, WIDE, 0>), grid, dim3(NW_ * 64), 0, st, BRA_DG2_HEAD_ARGS(g), g);  \
-        }                                                                                                                      \
-    } while (0)
-    if (nw == 16) {
-        if constexpr (WIDE != 0) { if (nl == 12) BRA_DG2(16, 12); else if (nl == 8) BRA_DG2(16, 8); else BRA_DG2(16, 4); }
-    }
-    else if (nw == 8) { if (nl == 12) BRA_DG2(8, 12); else if (nl == 10) BRA_DG2(8, 10); else if (nl == 8) BRA_DG2(8, 8); else BRA_DG2(8, 4); }
-    else { if (nl == 12) BRA_DG2(4, 12); else if (nl == 8) BRA_DG2(4, 8); else BRA_DG2(4, 4); }
-#undef BRA_DG2
+template <int I>
+static int dg2_launch_at(const DecGemm2Args& g, int grid, bra_stream_t st) {
+    constexpr Dg2Form f = dg2_form_at(I);
+    static_assert(dg2_slot(f) == I, "dg2_slot inverts dg2_form_at");
+    BRA_LAUNCH((dec_gemm2_kernel<f.mode, f.norm, f.act, f.outf32, f.nw, f.nl, f.wide, f.pk, f.fast, f.f8>), dim3(grid), dim3(f.nw * 64), 0, st,
+               BRA_DG2_HEAD_ARGS(g), g);
     return BRA_LAUNCH_STATUS();
+}
+template <int I>
+constexpr Dg2Launch dg2_launcher() {
+    if constexpr (dg2_kernel_exists(dg2_form_at(I))) return &dg2_launch_at<I>;
+    else return nullptr;
+}
+template <int... I>
+constexpr std::array<Dg2Launch, sizeof...(I)> dg2_launchers(std::integer_sequence<int, I...>) { return {{dg2_launcher<I>()...}}; }
+static constexpr auto DG2_TABLE = dg2_launchers(std::make_integer_sequence<int, DG2_SLOTS>{});
+
+static int launch_dg2(const Dg2Call& c, const DecGemm2Args& g, bra_stream_t st) {
+    Dg2Form f;
+    int grid;
+    const int rc = dg2_form_of(c, f, grid);
+    return rc ? rc : DG2_TABLE[dg2_slot(f)](g, grid, st);
 }
 
 }  // namespace bra
@@ -736,7 +652,7 @@ extern "C" int bra_dec_gemm2_fp8_rows(const void* x, long ldx, const float* ss_i
                                       const void* res, long ldres, void* out, long ldo, float* ss_out, int nss_out, int M, int N, int K,
                                       int act, int out_f32, int norm_folded, int image_rows, void* stream) {
     if (!Wq || !wscale) return BRA_ERR_ARG;
-    if (image_rows == 32 ? (M < 17 || M > 32) : (image_rows == 16 ? (M < 9 || M > 16) : (image_rows != 8 || M > 8))) return BRA_ERR_UNSUPPORTED;
+    if (M > 32 || image_rows != dg2_row_class(M)) return BRA_ERR_UNSUPPORTED;
     // (norm_w only selects the folded-norm form here: its values are never read when the weights carry it)
     return dec_gemm2_any(x, ldx, norm_folded ? ss_in : nullptr, norm_folded ? nss_in : 0, norm_folded ? Wq : nullptr, eps, Wq, K, res, ldres,
                          out, ldo, ss_out, nss_out, M, N, K, act, out_f32, norm_folded ? 3 : 1, nullptr, stream, wscale);
@@ -762,7 +678,6 @@ static int dec_gemm2_any(const void* x, long ldx, const float* ss_in, int nss_in
                         const void* W, long ldw, const void* res, long ldres, void* out, long ldo, float* ss_out,
                         int nss_out, int M, int N, int K, int act, int out_f32, int packed, void* probe, void* stream,
                         const float* wscale) {
-    (void)probe;
     // fp8 weights: the entry point pairs the row class of the image with M; packed, norm folded or absent
     if (wscale && (!(packed & 1) || (norm_w && !(packed & 2)))) return BRA_ERR_UNSUPPORTED;
     if (M <= 0 || M > 32 || N <= 0 || K <= 0 || K % 32 || ldx % 8 || ldw % 8 || !x || !W || !out) return BRA_ERR_ARG;
@@ -770,53 +685,14 @@ static int dec_gemm2_any(const void* x, long ldx, const float* ss_in, int nss_in
     if (out_f32 && res) return BRA_ERR_ARG;            // (out_f32 with ss_out: per-tile maxima of the logits, 16-column tiles)
     if (norm_w && (!ss_in || nss_in < 32 || nss_in % 32 || nss_in > 256)) return BRA_ERR_ARG;
     if (res && ldres % 4) return BRA_ERR_ARG;
-    const bool wide = M > 8;                     // 9 .. 16 rows: 16-column tiles everywhere (a diagonal tile holds 8 rows)
-    // 8-column (diagonal) tiles: dg2_diag_tiles (bra_decgemm.h)
-    const bool diag = !wide && !act && !out_f32 && K % 64 == 0 && dg2_diag_tiles(N);
+    const bool diag = dg2_diag(dg2_row_class(M), N, K, act, out_f32);
     if (ss_out && nss_out < (diag ? N / 8 : (N + 15) / 16)) return BRA_ERR_ARG;
     DecGemm2Args g = {(const bf16_t*)x, ldx, ss_in, nss_in, (const bf16_t*)norm_w, eps, (const bf16_t*)W, ldw,
                       (const bf16_t*)res, ldres, out, ldo, ss_out, nss_out, M, N, K, packed, wscale, BRA_DBG_INIT((unsigned long long*)probe) 1.f / (float)K};
     if (packed && (N % (diag ? 8 : 16) || K % (diag ? 64 : 32))) return BRA_ERR_ARG;
-    bra_stream_t st = (bra_stream_t)stream;
     if ((packed & 2) && !(packed & 1)) return BRA_ERR_ARG;
-    if (M > 16) {
-        // 17 .. 32 rows: the 16-row form's tiles, weights (bra_dec_pack_weights_rows(rows = 16)) and statistics rule, two row halves
-        // per weight fragment
-        if (norm_w && !(packed & 2)) return BRA_ERR_UNSUPPORTED;
-        if (norm_w) {
-            if (act) return launch_dg2<0, 2, 1, 0, 2>(g, st);
-            if (out_f32) return launch_dg2<0, 2, 0, 1, 2>(g, st);
-            return launch_dg2<0, 2, 0, 0, 2>(g, st);
-        }
-        if (act) return launch_dg2<0, 0, 1, 0, 2>(g, st);
-        if (out_f32) return launch_dg2<0, 0, 0, 1, 2>(g, st);
-        return launch_dg2<0, 0, 0, 0, 2>(g, st);
-    }
-    if (wide) {
-        // statistics only in the folded form (rstd in the epilogue); the weights must be packed for 16-column tiles
-        if (norm_w && !(packed & 2)) return BRA_ERR_UNSUPPORTED;
-        if (norm_w) {
-            if (act) return launch_dg2<0, 2, 1, 0, 1>(g, st);
-            if (out_f32) return launch_dg2<0, 2, 0, 1, 1>(g, st);
-            return launch_dg2<0, 2, 0, 0, 1>(g, st);
-        }
-        if (act) return launch_dg2<0, 0, 1, 0, 1>(g, st);
-        if (out_f32) return launch_dg2<0, 0, 0, 1, 1>(g, st);
-        return launch_dg2<0, 0, 0, 0, 1>(g, st);
-    }
-    if (norm_w && (packed & 2)) {            // RMSNorm weight folded into the packed weights, rstd applied in the epilogue
-        if (act) return launch_dg2<0, 2, 1, 0>(g, st);
-        if (out_f32) return launch_dg2<0, 2, 0, 1>(g, st);
-        return diag ? launch_dg2<1, 2, 0, 0>(g, st) : launch_dg2<0, 2, 0, 0>(g, st);
-    }
-    if (norm_w) {
-        if (act) return launch_dg2<0, 1, 1, 0>(g, st);
-        if (out_f32) return launch_dg2<0, 1, 0, 1>(g, st);
-        return diag ? launch_dg2<1, 1, 0, 0>(g, st) : launch_dg2<0, 1, 0, 0>(g, st);
-    }
-    if (act) return launch_dg2<0, 0, 1, 0>(g, st);
-    if (out_f32) return launch_dg2<0, 0, 0, 1>(g, st);
-    return diag ? launch_dg2<1, 0, 0, 0>(g, st) : launch_dg2<0, 0, 0, 0>(g, st);
+    // what is left to refuse is BRA_ERR_UNSUPPORTED: the call has no kernel (dg2_form_of)
+    return launch_dg2({M, N, K, act, out_f32, norm_w != nullptr, packed, wscale != nullptr, ldx, ldres, nss_in, probe != nullptr}, g, (bra_stream_t)stream);
 }
 
 extern "C" int bra_dec_pack_weights_rows(const void* W, long ldw, int N, int K, int act, int out_f32, const void* norm_w, int rows,
@@ -830,7 +706,7 @@ extern "C" int bra_dec_pack_weights(const void* W, long ldw, int N, int K, int a
 extern "C" int bra_dec_pack_weights_rows(const void* W, long ldw, int N, int K, int act, int out_f32, const void* norm_w, int rows,
                                          void* out, void* stream) {
     if (!W || !out || N <= 0 || K <= 0 || ldw % 8 || rows <= 0 || rows > 16) return BRA_ERR_ARG;
-    const bool diag = rows <= 8 && !act && !out_f32 && K % 64 == 0 && dg2_diag_tiles(N);      // bra_dec_gemm2's rule
+    const bool diag = dg2_diag(rows, N, K, act, out_f32);
     if (N % (diag ? 8 : 16) || K % (diag ? 64 : 32)) return BRA_ERR_UNSUPPORTED;
     const long nchunk = (long)N * K / 8;
     const dim3 grid((unsigned)((nchunk + 255) / 256));
@@ -846,14 +722,12 @@ extern "C" int bra_dec_pack_weights_rows(const void* W, long ldw, int N, int K, 
 extern "C" int bra_dec_pack_weights_fp8_rows(const void* W, long ldw, int N, int K, int act, int out_f32, const void* norm_w, int rows,
                                              void* out_q, float* out_scale, void* stream) {
     if (!W || !out_q || !out_scale || N <= 0 || K <= 0 || ldw % 8 || rows <= 0 || rows > 16) return BRA_ERR_ARG;
-    const bool wide = rows > 8;
-    const bool diag = !wide && !act && !out_f32 && K % 64 == 0 && dg2_diag_tiles(N);      // bra_dec_gemm2's rule
+    const bool diag = dg2_diag(rows, N, K, act, out_f32);
     if (N % (diag ? 8 : 16) || K % (diag ? 128 : 64)) return BRA_ERR_UNSUPPORTED;
-    {   // only what bra_dec_gemm2_fp8_rows streams: K exactly one register round of the (waves, chunks) the launcher picks
-        int nw, nl;
-        const int nsteps = K / (diag ? 64 : 32);
-        dg2_waves_and_chunks(nsteps, wide, nw, nl);
-        if (nsteps != nw * nl || nl % 2 || (!wide && nw == 16)) return BRA_ERR_UNSUPPORTED;
+    {   // only what bra_dec_gemm2_fp8_rows streams against `rows` rows
+        Dg2Form f;
+        int grid;
+        if (dg2_form_of({rows, N, K, act, out_f32, norm_w != nullptr, norm_w ? 3 : 1, 1, K, 0, 32, 0}, f, grid)) return BRA_ERR_UNSUPPORTED;
     }
     bra_stream_t st = (bra_stream_t)stream;
     BRA_LAUNCH(dec_rowscale_fp8_kernel, dim3((N + 3) / 4), dim3(256), 0, st, (const bf16_t*)W, ldw, N, K, (const bf16_t*)norm_w, out_scale);
@@ -879,8 +753,27 @@ extern "C" int bra_dec_stat_cols(int H) {
     return nss > 256 ? 0 : nss;
 }
 
-extern "C" int bra_dec_gemm2_rows32_ok(int K, int normed, int packed) { return dg2_rows32_ok(K, normed != 0, packed != 0) ? 1 : 0; }
-extern "C" int bra_dec_gemm2_fp8_rows32_ok(int K, int normed) { return dg2_fp8_rows32_ok(K, normed != 0) ? 1 : 0; }
+// the form of a call (see Dg2Call; the arguments are taken as valid) without launching anything: form[10] = dec_gemm2_kernel's template
+// arguments in their order, or BRA_ERR_UNSUPPORTED.  The plan queries of the 32-row class are this question at M = 32.
+static int dg2_form_query(const Dg2Call& c, int* form) {
+    Dg2Form f;
+    int grid;
+    const int rc = dg2_form_of(c, f, grid);
+    if (!rc && form) { const int v[10] = {f.mode, f.norm, f.act, f.outf32, f.nw, f.nl, f.wide, f.pk, f.fast, f.f8}; for (int i = 0; i < 10; ++i) form[i] = v[i]; }
+    return rc;
+}
+#ifdef BRA_DEBUG
+extern "C" int bra_dec_gemm2_form(int M, int N, int K, int act, int out_f32, int normed, int packed, int fp8, long ldx, long ldres, int nss_in,
+                                  int probed, int* form) {
+    return dg2_form_query({M, N, K, act, out_f32, normed, packed, fp8, ldx, ldres, nss_in, probed}, form);
+}
+#endif
+extern "C" int bra_dec_gemm2_rows32_ok(int K, int normed, int packed) {
+    return K > 0 && K % 32 == 0 && !dg2_form_query({32, 16, K, 0, 0, normed, (packed ? 1 : 0) | (normed ? 2 : 0), 0, K, 0, 32, 0}, nullptr);
+}
+extern "C" int bra_dec_gemm2_fp8_rows32_ok(int K, int normed) {
+    return K > 0 && K % 32 == 0 && !dg2_form_query({32, 16, K, 0, 0, normed, normed ? 3 : 1, 1, K, 0, 32, 0}, nullptr);
+}
 
 extern "C" int bra_row_sumsq(const void* x, long ldx, int M, int K, float* ss, int nss, void* stream) {
     if (M <= 0 || M > 32 || K <= 0 || K % 8 || ldx % 8 || !x || !ss || nss < 1) return BRA_ERR_ARG;

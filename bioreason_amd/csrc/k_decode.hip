@@ -88,7 +88,7 @@ static StepGemms step_gemms(float* ss_ws, int nss, int B, int H, int Nq, int Nqk
     const int nblk = bra::dg2_diag_tiles(H) ? H / 8 : (H + 15) / 16;      // workgroups of an N = H projection (bra_dec_gemm2's tile rule)
     s.v2 = ss_ws && B <= 32 && nss >= 32 && nss % 32 == 0 && nss <= 256 && nss >= nblk;
     // two statistics arrays [rows][nss], rows = 8, (9 .. 16 sequences) 16 or (17 .. 32 sequences: the 32-row projections) 32
-    s.ssx = ss_ws; s.ssh = ss_ws ? ss_ws + (B > 16 ? 32 : (B > 8 ? 16 : 8)) * (long)nss : nullptr; s.nss = nss;
+    s.ssx = ss_ws; s.ssh = ss_ws ? ss_ws + bra::dg2_row_class(B) * (long)nss : nullptr; s.nss = nss;
     s.B = B; s.H = H; s.Nq = Nq; s.Nqkv = Nqkv; s.F = F; s.V = V; s.eps = eps; s.stream = stream;
     return s;
 }
@@ -98,13 +98,22 @@ static int sg_begin(const StepGemms& s, const void* x) {
 // is this projection of the layer an e4m3 image?  flags bit 3: all four are; bit 5: the ones whose scale pointer is set
 static bool sg_is_fp8(const Layer& l, const float* sc) { return (l.flags & 8) || ((l.flags & 32) && sc); }
 // row class of the fp8 images a step of B rows streams (bra_dec_gemm2_fp8_rows; 32: the rows = 16 images against 17 .. 32 rows)
-static int sg_image_rows(const StepGemms& s) { return s.B > 16 ? 32 : (s.B > 8 ? 16 : 8); }
+static int sg_image_rows(const StepGemms& s) { return bra::dg2_row_class(s.B); }
+// one projection of the second-generation step over its own image — e4m3 with row scales `sc` (sg_is_fp8) or bf16 packed per `pk` — in the
+// same step.  ss_in != null: the input's statistics, its RMSNorm `ln` (folded into an e4m3 image); res / ss_out: [B, H] rows / statistics
+static int sg_proj(const StepGemms& s, const Layer& l, const float* sc, const void* in, int K, const float* ss_in, const void* ln, const void* W,
+                   const void* res, void* out, long ldo, float* ss_out, int N, int act, int pk) {
+    const int nin = ss_in ? s.nss : 0, nout = ss_out ? s.nss : 0;
+    const long ldres = res ? s.H : 0;
+    const float eps = ss_in ? s.eps : 0.f;
+    if (sg_is_fp8(l, sc))
+        return bra_dec_gemm2_fp8_rows(in, K, ss_in, nin, eps, W, sc, res, ldres, out, ldo, ss_out, nout, s.B, N, K, act, 0, ss_in != nullptr,
+                                      sg_image_rows(s), s.stream);
+    return bra_dec_gemm2_packed(in, K, ss_in, nin, ln, eps, W, K, res, ldres, out, ldo, ss_out, nout, s.B, N, K, act, 0, pk, s.stream);
+}
 static int sg_qkv(const StepGemms& s, const Layer& l, const void* x, void* qkv) {
     const int pk = l.flags & 3;
-    if (s.v2 && sg_is_fp8(l, l.sc_qkv))
-        return bra_dec_gemm2_fp8_rows(x, s.H, s.ssx, s.nss, s.eps, l.Wqkv, l.sc_qkv, nullptr, 0, qkv, s.Nqkv, nullptr, 0, s.B, s.Nqkv, s.H, 0, 0, 1,
-                                      sg_image_rows(s), s.stream);
-    if (s.v2) return bra_dec_gemm2_packed(x, s.H, s.ssx, s.nss, l.ln1, s.eps, l.Wqkv, s.H, nullptr, 0, qkv, s.Nqkv, nullptr, 0, s.B, s.Nqkv, s.H, 0, 0, pk, s.stream);
+    if (s.v2) return sg_proj(s, l, l.sc_qkv, x, s.H, s.ssx, l.ln1, l.Wqkv, nullptr, qkv, s.Nqkv, nullptr, s.Nqkv, 0, pk);
     if (pk) return BRA_ERR_UNSUPPORTED;
     return bra_dec_gemm(x, s.H, l.ln1, s.eps, l.Wqkv, s.H, nullptr, 0, qkv, s.Nqkv, s.B, s.Nqkv, s.H, 0, 0, s.stream);
 }
@@ -112,19 +121,10 @@ static int sg_qkv(const StepGemms& s, const Layer& l, const void* x, void* qkv) 
 static int sg_tail(const StepGemms& s, const Layer& l, const void* o, void* x, void* h, void* act) {
     int rc;
     const int pk = l.flags & 1;
-    if (s.v2) {     // each projection over its own image: e4m3 (bra_dec_gemm2_fp8_rows) or bf16 packed, in the same step
-        const int ir = sg_image_rows(s);
-        rc = sg_is_fp8(l, l.sc_o)
-                 ? bra_dec_gemm2_fp8_rows(o, s.Nq, nullptr, 0, 0.f, l.Wo, l.sc_o, x, s.H, h, s.H, s.ssh, s.nss, s.B, s.H, s.Nq, 0, 0, 0, ir, s.stream)
-                 : bra_dec_gemm2_packed(o, s.Nq, nullptr, 0, nullptr, 0.f, l.Wo, s.Nq, x, s.H, h, s.H, s.ssh, s.nss, s.B, s.H, s.Nq, 0, 0, pk, s.stream);
-        if (rc) return rc;
-        rc = sg_is_fp8(l, l.sc_gu)
-                 ? bra_dec_gemm2_fp8_rows(h, s.H, s.ssh, s.nss, s.eps, l.Wgu, l.sc_gu, nullptr, 0, act, s.F, nullptr, 0, s.B, 2 * s.F, s.H, 1, 0, 1, ir, s.stream)
-                 : bra_dec_gemm2_packed(h, s.H, s.ssh, s.nss, l.ln2, s.eps, l.Wgu, s.H, nullptr, 0, act, s.F, nullptr, 0, s.B, 2 * s.F, s.H, 1, 0, l.flags & 3, s.stream);
-        if (rc) return rc;
-        return sg_is_fp8(l, l.sc_d)
-                   ? bra_dec_gemm2_fp8_rows(act, s.F, nullptr, 0, 0.f, l.Wd, l.sc_d, h, s.H, x, s.H, s.ssx, s.nss, s.B, s.H, s.F, 0, 0, 0, ir, s.stream)
-                   : bra_dec_gemm2_packed(act, s.F, nullptr, 0, nullptr, 0.f, l.Wd, s.F, h, s.H, x, s.H, s.ssx, s.nss, s.B, s.H, s.F, 0, 0, pk, s.stream);
+    if (s.v2) {
+        if ((rc = sg_proj(s, l, l.sc_o, o, s.Nq, nullptr, nullptr, l.Wo, x, h, s.H, s.ssh, s.H, 0, pk))) return rc;
+        if ((rc = sg_proj(s, l, l.sc_gu, h, s.H, s.ssh, l.ln2, l.Wgu, nullptr, act, s.F, nullptr, 2 * s.F, 1, l.flags & 3))) return rc;
+        return sg_proj(s, l, l.sc_d, act, s.F, nullptr, nullptr, l.Wd, h, x, s.H, s.ssx, s.H, 0, pk);
     }
     if (pk) return BRA_ERR_UNSUPPORTED;
     if ((rc = bra_dec_gemm(o, s.Nq, nullptr, 0.f, l.Wo, s.Nq, x, s.H, h, s.H, s.B, s.H, s.Nq, 0, 0, s.stream))) return rc;

@@ -190,15 +190,11 @@ def rollout_weights(model, rows: int = 8):
     pack = _switch("BRA_DEC_PACK") == "1"
     wide = rows > 8             # 9 .. 32 sequences: every projection is packed for 16-column tiles (ops.dec_pack_weights(rows=16));
     #                             the 32-row projections stream the same image — there is no second copy of the rollout weights
-    # fp8 images exist in the 8-row and in the 16-row class (ops.dec_pack_weights_fp8(rows=16); BRA_FP8_WIDE=0: bf16 at 9 .. 16 rows)
-    # 17 .. 32 rows stream the rows = 16 e4m3 images (image_rows = 32): the SAME set and the same cache entry as at 9 .. 16 rows
-    # (BRA_FP8_ROWS32=0: generate() keeps 16-row chunks and never asks for more rows; asked anyway, the images are bf16)
-    fp8 = rollout_fp8_enabled(model) and pack and rows <= MAX_DECODE_ROWS32 and (not wide or _switch("BRA_FP8_WIDE") == "1") \
-        and (rows <= MAX_DECODE_ROWS or _switch("BRA_FP8_ROWS32") == "1")
-    # ... except where a 16-row image has no 32-row form — the folded norm at a hidden size of 6144: those projections keep their bf16
-    # packed image at 17 .. 32 rows, a set of its own
-    no32 = bool(fp8 and rows > MAX_DECODE_ROWS and fp8_rows32_form_exists(eng.H, False) and not fp8_rows32_form_exists(eng.H, True))
-    key = (model._packed_sig, model._lora_enabled, pack, wide, fp8, no32,
+    # the e4m3 images.  17 .. 32 rows stream the rows = 16 images: the SAME set and cache entry as at 9 .. 16 rows, except where an image has
+    # no 32-row form — the folded norm at a hidden size of 6144: those projections keep their bf16 packed image there, a set of its own
+    e4m3 = {nm: _streams_e4m3(model, rows, K, normed)
+            for nm, K, normed in (("Wqkv", eng.H, True), ("Wo", eng.Nq, False), ("Wgu", eng.H, True), ("Wd", eng.F, False))}
+    key = (model._packed_sig, model._lora_enabled, pack, wide, tuple(e4m3.values()),
            None if arena is None or arena.params is None else (arena.step_count, arena.params._version))
     cached = getattr(eng, "_rollout", None)
     if cached is not None and cached[0] == key:
@@ -226,7 +222,7 @@ def rollout_weights(model, rows: int = 8):
             # projection by projection: one whose shape the fp8 kernel does not take (K beyond one register round: Qwen3-4B's down
             # projection) keeps its bf16 packed image and the step streams both kinds (`fp8_proj`: the names that are e4m3)
             q8 = {nm: ops.dec_pack_weights_fp8(rec[nm], act=(nm == "Wgu"), norm_w=nws[nm], rows=prows)
-                  if fp8 and not (no32 and nws[nm] is not None) else None for nm in names}
+                  if e4m3[nm] else None for nm in names}
             pk = {nm: ops.dec_pack_weights(rec[nm], act=(nm == "Wgu"), norm_w=nws[nm], rows=prows) for nm in names if q8[nm] is None}
             if all(v is not None for v in pk.values()):
                 rec.update({nm + "_p": v for nm, v in pk.items()})
@@ -320,9 +316,8 @@ class _FusedStepState:
             if kp is not None:
                 d.kp, d.vtp = kp[i].data_ptr(), vtp[i].data_ptr()
         if use_packed and (B > 8 or _switch("BRA_DEC_PACK_HEAD") == "1"):      # (above 8 rows only the packed head streams)
-            # (fp32-output projections use 16-column tiles in both row classes: one fp8 image of the head serves 1 .. 16 rows)
-            # (17 .. 32 rows: the same image, streamed with the 32-row class where that form exists for the hidden size)
-            h8_rows = B <= MAX_DECODE_ROWS or fp8_rows32_form_exists(eng.H, True)
+            # (fp32-output projections use 16-column tiles in every row class: one fp8 image of the head serves 1 .. 16 rows, and 17 .. 32 where that form exists)
+            h8_rows = B <= MAX_DECODE_ROWS or _streams_e4m3(model, B, eng.H, True)
             h8 = packed_head_fp8(model, rows=B) if (h8_rows and all(R.get("fp8_proj") for R in self.rw)) else None
             if h8 is not None:
                 self.head_p, self.head_s = h8
@@ -529,7 +524,7 @@ def decode_rows_limit() -> int:
 
 def rows32_form_exists(K: int, normed: bool, packed: bool = True) -> bool:
     """does bra_dec_gemm2 have a 32-row kernel (17 .. 32 rows over 16-column tiles of 32 k) for this K?  The library's own answer
-    (bra_dec_gemm2_rows32_ok: the rule launch_dg2 dispatches by); `normed`: the folded norm, `packed`: fragment-ordered weights"""
+    (bra_dec_gemm2_rows32_ok: the rule the launcher dispatches by); `normed`: the folded norm, `packed`: fragment-ordered weights"""
     return bool(get_lib()._dll.bra_dec_gemm2_rows32_ok(int(K), int(normed), int(packed)))
 
 
@@ -539,25 +534,30 @@ def fp8_rows32_form_exists(K: int, normed: bool) -> bool:
     return bool(get_lib()._dll.bra_dec_gemm2_fp8_rows32_ok(int(K), int(normed)))
 
 
+def _streams_e4m3(model, rows: int, K: int, normed: bool) -> bool:
+    """does a projection of this K (`normed`: its input's norm folded in) stream its e4m3 image in a token loop of `rows` sequences, or its
+    bf16 packed image?  An fp8 rollout over packed weights: <= 8 rows wherever the 8-row packer takes the shape; 9 .. 16 rows (BRA_FP8_WIDE)
+    the rows = 16 image, at the single-round K; 17 .. 32 rows (BRA_FP8_ROWS32) the same image where the library has the 32-row form"""
+    if not (rollout_fp8_enabled(model) and _switch("BRA_DEC_PACK") == "1"):
+        return False
+    if rows <= MAX_DECODE_ROWS:
+        return rows <= 8 or (_switch("BRA_FP8_WIDE") == "1" and fp8_rows32_form_exists(K, False))
+    return rows <= MAX_DECODE_ROWS32 and _switch("BRA_FP8_WIDE") == "1" and _switch("BRA_FP8_ROWS32") == "1" and fp8_rows32_form_exists(K, normed)
+
+
 def _one_loop_ok(model, B: int) -> bool:
     """17 .. 32 rows in ONE token loop: what the 32-row projections need is folded, fragment-packed rollout weights and the
     second-generation statistics workspace; anything else (BRA_DEC_PACK = 0, BRA_DEC_GEMM_V1, a shape the packer
     refuses, an fp8 rollout under BRA_FP8_ROWS32=0) keeps the 16-row chunks"""
     eng = model.ensure_packed()
-    fp8 = rollout_fp8_enabled(model)
-    if _norm_stat_nss(eng) == 0 or (fp8 and _switch("BRA_FP8_ROWS32") != "1"):
+    if _norm_stat_nss(eng) == 0 or (rollout_fp8_enabled(model) and _switch("BRA_FP8_ROWS32") != "1"):
         return False
     # the K of every projection must select a 32-row form the library has (bra_dec_gemm2 returns BRA_ERR_UNSUPPORTED otherwise, and
     # only at launch time): normed inputs (hidden size: qkv, gate/up, lm_head) and plain ones (q width: o; intermediate size: down).
     # In an fp8 rollout a projection streams its e4m3 image where the 32-row fp8 form exists and its bf16 packed image otherwise
-    # (rollout_weights), so either form will do; the bf16 answer alone is asked where no e4m3 image is built (BRA_FP8_WIDE=0)
-    f8 = fp8 and _switch("BRA_FP8_WIDE") == "1"
-
-    def form(K, normed):
-        return (f8 and fp8_rows32_form_exists(K, normed)) or rows32_form_exists(K, normed=normed)
-    if not (form(eng.H, True) and form(eng.Nq, False) and form(eng.F, False)):
-        return False
-    return _packed_ok(B, rollout_weights(model, rows=B))         # (the same wide image a 9 .. 16-row loop builds and caches)
+    # (rollout_weights), so either form will do
+    forms = all(_streams_e4m3(model, B, K, n) or rows32_form_exists(K, normed=n) for K, n in ((eng.H, True), (eng.Nq, False), (eng.F, False)))
+    return forms and _packed_ok(B, rollout_weights(model, rows=B))         # (the same wide image a 9 .. 16-row loop builds and caches)
 
 
 def _row_chunks(B: int, prompt_alias, max_rows: int = MAX_DECODE_ROWS):

@@ -56,6 +56,12 @@ int bra_attn_set_probe(void* buf);
 int bra_dec_gemm2_probe(const void* x, long ldx, const float* ss_in, int nss_in, const void* norm_w, float eps, const void* W,
                         long ldw, const void* res, long ldres, void* out, long ldo, float* ss_out, int nss_out, int M, int N,
                         int K, int act, int out_f32, int packed, void* probe, void* stream);
+/* which kernel bra_dec_gemm2 / _packed / _fp8_rows / _probe would launch for a call, launching nothing: form[10] receives
+ * dec_gemm2_kernel's template arguments in their order {MODE, NORM, ACT, OUTF32, NW, NL, WIDE, PK, FAST, F8}, or the call's refusal
+ * (BRA_ERR_UNSUPPORTED) is returned.  The arguments are those the choice depends on and are taken as valid (`normed`: a norm weight
+ * is given, `packed`: as bra_dec_gemm2_packed, `fp8`: an e4m3 image, `probed`: a timing probe is attached). */
+int bra_dec_gemm2_form(int M, int N, int K, int act, int out_f32, int normed, int packed, int fp8, long ldx, long ldres, int nss_in,
+                       int probed, int* form);
 /* diagnostics: 16 x 8-byte device buffer that bra_dec_attn_both stamps with the 100 MHz wall clock (one prompt-part wave:
  * entry, requests issued, q arrived, q rotated, scores, partials issued; one completion-part wave: entry, prologue, scores,
  * end); null switches the probe off.  Process-wide. */

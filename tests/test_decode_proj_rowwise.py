@@ -45,7 +45,8 @@ unmasked tile maximum: each moves a few elements and passes there.  Here every e
           rsqrt(sum of ALL columns / K + eps) within tau_rstd u, at nss_in = 32, 64, 160, 256 and M = 5 .. 32 (which row, which columns,
           which of the eight groups, rs_lds[16 + ..] for rows 16 .. 31); NORM 1 through a one-hot W: out = w_k x_mk bf16(rstd_m).
 
-The dispatch mirror (_mirror) restates dg2_waves_and_chunks, dg2_diag_tiles, dg2_rows32_ok and launch_dg2's decision:
+The dispatch mirror (_mirror) restates, independently, what bra_decgemm.h states once (dg2_waves_and_chunks, dg2_diag, dg2_kernel_exists,
+dg2_form_of):
     fast     packed, no in-register norm, K exactly one register round (waves x chunks k-steps): the FAST instantiation
     single   K exactly one round through the general kernel (row-major weights or NORM 1)
     clamped  one round with steps past K clamped and zeroed
@@ -53,14 +54,16 @@ The dispatch mirror (_mirror) restates dg2_waves_and_chunks, dg2_diag_tiles, dg2
 A form is (rows class 8 / 16 / 32, tile mode, waves, chunks, kind, NORM, packed, epilogue).  _reachable() walks every K % 32 == 0 up to 9728
 (the exact set's limit and the largest K of a supported model); FORM_CASES picks the smallest case of every form and
 test_every_reachable_form_has_a_case proves the two sets equal; every form the launcher refuses is asserted refused
-(test_refused_forms_are_refused, test_rows32_refusals_follow_the_exported_rule).  Two instantiations of launch_dg2's table are never
-selected by dg2_waves_and_chunks: BRA_DG2(16, 4) (16 waves have at least 8 steps each) and, for the same reason, BRA_DG2(8, 4).
+(test_refused_forms_are_refused, test_rows32_refusals_follow_the_exported_rule); test_exported_form_is_the_mirrors reads the launcher's
+choice itself (bra_dec_gemm2_form, no launch) at every call of the walk.  dg2_waves_and_chunks never selects (16, 4) (16 waves have at
+least 8 steps each) or, for the same reason, (8, 4): there are no such kernels (tests/test_isa.py holds the compiled set to the list).
 <= 8 rows with a bf16 epilogue and K % 64 == 0 reach 16-column tiles only at N = 2064 (packed) or N % 8 != 0 (row-major, N = 44).
 
 Emulator cases above 4.3e6 weight elements are skipped (`emulator: ...`); the mirror names a smaller case of the same form for each.
 Worst device ratios go to dec_proj_rowwise_ratios.json in BRA_TEST_EVIDENCE_DIR (else test_evidence/).
 """
 import collections
+import ctypes
 import functools
 import json
 import math
@@ -125,7 +128,7 @@ def _diag(M, N, K, act, f32):
 
 @functools.lru_cache(maxsize=None)
 def _rows32_ok(K, normed, packed):
-    """dg2_rows32_ok"""
+    """17 .. 32 rows: is there a kernel for this K?  (the library's answer: bra_dec_gemm2_rows32_ok)"""
     if K <= 0 or K % 32:
         return False
     nsteps = K // 32
@@ -156,7 +159,9 @@ def _form_of(M, N, K, epi, norm, packed, fp8=False):
     kind = "multi" if rounds > 1 else ("fast" if fast else ("single" if nsteps == nw * nl else "clamped"))
     refused = (rows > 8 and NORM == 1) or (NORM == 2 and rounds != 1) or (rows == 32 and not _rows32_ok(K, NORM == 2, bool(packed & 1)))
     if fp8:
-        refused = refused or M > 8 or not fast or nl % 2 == 1 or nw == 16
+        # e4m3 images: packed, norm folded or absent, the fast form alone (an even number of chunks: two k-steps per request), in every
+        # row class — 17 .. 32 rows where the bf16 rule above has the fast form too (not the folded norm on 16 waves x 12 chunks)
+        refused = refused or not fast or nl % 2 == 1 or not (packed & 1) or (rows == 8 and nw == 16)
     return Form(rows, int(diag), nw, nl, kind, NORM, packed, epi), refused, ntiles, min(ntiles, gmax), rounds
 
 
@@ -619,6 +624,56 @@ def test_rows32_every_k(backend, K):
         assert rc == UNSUPPORTED, (K, norm, packed, rc)
         win.result(f"rows32-{K}")
     _assert_ratios(f"rows32-{K}", ratios, backend)
+
+
+def _exported_form(lib, M, N, K, epi, norm, packed, fp8=False, ldx=None, probed=0):
+    """bra_dec_gemm2_form (debug ABI; launches nothing) -> dec_gemm2_kernel's ten template arguments, or the refusal code"""
+    form = (ctypes.c_int * 10)()
+    rc = int(lib._dll.bra_dec_gemm2_form(M, N, K, int(epi == "act"), int(epi in ("f32", "f32max")), int(norm), packed, int(fp8), ldx or K,
+                                         N if epi == "res" else 0, 32 if norm else 0, probed, ctypes.addressof(form)))
+    return rc if rc else tuple(form)
+
+
+def _form_walk():
+    """every call of _reachable()'s walk (the row count rotating over the class), then the e4m3 calls of the three row classes"""
+    for rows in (8, 16, 32):
+        for (norm, packed) in NORM_PACKED:
+            for fp8 in ((False, True) if packed & 1 and (packed & 2 or not norm) else (False,)):
+                for epi in EPIS:
+                    for K in range(32, K_MAX + 1, 32):
+                        for N in _shape_candidates(rows, epi, packed):
+                            M = M_OF[rows][(K // 32) % len(M_OF[rows])]
+                            if not (packed and N % (8 if _diag(M, N, K, epi == "act", epi in ("f32", "f32max")) else 16)):
+                                yield M, N, K, epi, norm, packed, fp8
+
+
+def test_exported_form_is_the_mirrors(debug_backend):
+    """the launcher's own choice, read through bra_dec_gemm2_form without a launch, equals the mirror's at every call of the walk: row class,
+    tile mode, waves, chunks, kind, NORM, packed, fp8, and refusal"""
+    lib = _lib.get_lib()
+    seen = set()
+    for (M, N, K, epi, norm, packed, fp8) in _form_walk():
+        f, refused = _form_of(M, N, K, epi, norm, packed, fp8)[:2]
+        got = _exported_form(lib, M, N, K, epi, norm, packed, fp8)
+        assert (got == UNSUPPORTED) == refused, (M, N, K, epi, norm, packed, fp8, got)
+        if refused:
+            continue
+        mode, NORM, act, f32, nw, nl, wide, pk, fast, f8 = got
+        nsteps = K // (64 if mode else 32)
+        kind = "fast" if fast else ("multi" if nsteps > nw * nl else ("single" if nsteps == nw * nl else "clamped"))
+        assert ({0: 8, 1: 16, 2: 32, 3: 32}[wide], mode, nw, nl, kind, NORM, pk, f8) == (f.rows, f.mode, f.nw, f.nl, f.kind, f.norm, packed & 1, int(fp8)), \
+            (M, N, K, epi, norm, packed, fp8, got)
+        assert (act, f32) == (int(epi == "act"), int(epi in ("f32", "f32max"))) and (wide == 3) == (f.rows == 32 and kind == "multi")
+        seen.add(got)
+    assert len(seen) > 400
+    # outside the walk's strides: a probed call and one whose row pitch does not fit 24 bits leave the fast form for the general kernel,
+    # which 32 rows have in the (waves, chunks) of at most 64 steps only
+    assert _exported_form(lib, 8, 48, 512, "f32", False, 1)[6:] == (0, 1, 1, 0)
+    assert _exported_form(lib, 8, 48, 512, "f32", False, 1, probed=1)[6:] == (0, 1, 0, 0)
+    assert _exported_form(lib, 8, 48, 512, "f32", False, 1, ldx=1 << 24)[6:] == (0, 1, 0, 0)
+    assert _exported_form(lib, 32, 48, 2048, "f32", True, 3, ldx=1 << 24)[4:] == (8, 8, 2, 1, 0, 0)
+    assert _exported_form(lib, 32, 48, 2560, "f32", True, 3, ldx=1 << 24) == UNSUPPORTED
+    assert _exported_form(lib, 8, 48, 512, "f32", False, 1, fp8=True, ldx=1 << 24) == UNSUPPORTED
 
 
 # ----------------------------------------------------------------------------- 2: shapes the forms' smallest cases do not reach

@@ -6,8 +6,11 @@ import os
 import re
 import shutil
 import subprocess
+import sys
 
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bioreason_amd", "csrc")
@@ -84,6 +87,31 @@ def test_fast_decode_projections_request_weights_before_any_argument_fetch(tmp_p
             assert len([i for i in seg_loads if i < first_ld]) <= 1, n
             continue
         assert not seg_loads or seg_loads[0] > first_ld, n                   # ... and before anything is fetched from the segment
+
+
+def test_compiled_decode_projections_are_exactly_the_forms_the_launcher_names(tmp_path, emu_lib_path):
+    """the dec_gemm2_kernel instantiations in the product's device code are the forms bra_dec_gemm2_form names over the dispatch walk of
+    tests/test_decode_proj_rowwise.py — once with small strides, once with a row pitch of 2^24, which leaves the fast form — no more (a
+    kernel nothing can launch is compiled, shipped and loaded for nothing) and no fewer"""
+    from bioreason_amd import _lib
+    from test_decode_proj_rowwise import _form_walk, _exported_form
+    compiled = set()
+    for n in _kernels(_asm("k_decgemm.hip", tmp_path)):
+        m = re.search(r"dec_gemm2_kernelI((?:Li\d+E){10})E", n)
+        if m:
+            compiled.add(tuple(int(v) for v in re.findall(r"Li(\d+)E", m.group(1))))
+    lib = _lib.use_library_for_tests(emu_lib_path)
+    try:
+        named = set()
+        for (M, N, K, epi, norm, packed, fp8) in _form_walk():
+            for ldx in (K, 1 << 24):
+                got = _exported_form(lib, M, N, K, epi, norm, packed, fp8, ldx=ldx)
+                if isinstance(got, tuple):
+                    named.add(got)
+    finally:
+        _lib.reset_library()
+    assert len(named) > 500
+    assert compiled == named, (sorted(compiled - named)[:8], sorted(named - compiled)[:8])
 
 
 def test_four_wave_gemm_keeps_its_tile_in_registers_and_its_memory_instructions_inside_the_mfma_clusters(tmp_path):
