@@ -745,6 +745,22 @@ extern "C" int bra_dec_pack_weights_fp8(const void* W, long ldw, int N, int K, i
     return bra_dec_pack_weights_fp8_rows(W, ldw, N, K, act, out_f32, norm_w, 8, out_q, out_scale, stream);
 }
 
+// the e4m3 image of a plain projection (no norm, bf16 output) at ANY K % 64 == 0, for bra_dec_gemm2_fp8_anyk (k_decgemm8.hip): the quantiser
+// and the rows = 16 order of bra_dec_pack_weights_fp8_rows without its single-round check — at a K both take, the same bytes
+extern "C" int bra_dec_gemm2_fp8_anyk_ok(int N, int K);
+extern "C" int bra_dec_pack_weights_fp8_anyk(const void* W, long ldw, int N, int K, void* out_q, float* out_scale, void* stream) {
+    if (!W || !out_q || !out_scale || N <= 0 || K <= 0 || ldw % 8) return BRA_ERR_ARG;
+    if (!bra_dec_gemm2_fp8_anyk_ok(N, K)) return BRA_ERR_UNSUPPORTED;
+    bra_stream_t st = (bra_stream_t)stream;
+    BRA_LAUNCH(dec_rowscale_fp8_kernel, dim3((N + 3) / 4), dim3(256), 0, st, (const bf16_t*)W, ldw, N, K, (const bf16_t*)nullptr, out_scale);
+    const int rc = BRA_LAUNCH_STATUS();
+    if (rc) return rc;
+    const long nchunk = (long)N * K / 16;
+    BRA_LAUNCH((dec_pack_fp8_kernel<0>), dim3((unsigned)((nchunk + 255) / 256)), dim3(256), 0, st, (const bf16_t*)W, ldw, N, K, (const bf16_t*)nullptr,
+               out_scale, (unsigned*)out_q);
+    return BRA_LAUNCH_STATUS();
+}
+
 // statistics columns of a step whose hidden size is H: the workgroups of an N = H projection (one partial each), as a multiple of 32;
 // 0 where that is more than the 256 a consumer folds (the step then runs the first-generation projections)
 extern "C" int bra_dec_stat_cols(int H) {

@@ -106,9 +106,16 @@ static int sg_proj(const StepGemms& s, const Layer& l, const float* sc, const vo
     const int nin = ss_in ? s.nss : 0, nout = ss_out ? s.nss : 0;
     const long ldres = res ? s.H : 0;
     const float eps = ss_in ? s.eps : 0.f;
-    if (sg_is_fp8(l, sc))
+    if (sg_is_fp8(l, sc)) {
+        // a plain projection whose K has no single-round e4m3 form in this row class streams the any-K image (k_decgemm8.hip): the host
+        // packed it with bra_dec_pack_weights_fp8_anyk exactly there (the question bra_dec_pack_weights_fp8_rows asks)
+        bra::Dg2Form f;
+        int grid;
+        if (!ss_in && !act && bra::dg2_form_of({s.B, N, K, 0, 0, 0, 1, 1, K, 0, 32, 0}, f, grid))
+            return bra_dec_gemm2_fp8_anyk(in, K, W, sc, res, ldres, out, ldo, ss_out, nout, s.B, N, K, s.stream);
         return bra_dec_gemm2_fp8_rows(in, K, ss_in, nin, eps, W, sc, res, ldres, out, ldo, ss_out, nout, s.B, N, K, act, 0, ss_in != nullptr,
                                       sg_image_rows(s), s.stream);
+    }
     return bra_dec_gemm2_packed(in, K, ss_in, nin, ln, eps, W, K, res, ldres, out, ldo, ss_out, nout, s.B, N, K, act, 0, pk, s.stream);
 }
 static int sg_qkv(const StepGemms& s, const Layer& l, const void* x, void* qkv) {

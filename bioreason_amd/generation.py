@@ -34,6 +34,7 @@ _SWITCHES = {
     "BRA_DEC_ROWS32": "0",          # 1: 17 .. 32 sequences in one token loop
     "BRA_FP8_WIDE": "1",            # 0: an fp8 rollout streams bf16 images at 9 .. 16 sequences (as before the 16-row fp8 form)
     "BRA_FP8_ROWS32": "1",          # 0: an fp8 rollout of 17+ sequences keeps 16-row chunks under BRA_DEC_ROWS32=1 (no effect without it)
+    "BRA_FP8_ANYK": "0",            # 1: an fp8 rollout streams o / down as e4m3 at any K % 64 == 0 (bra_dec_gemm2_fp8_anyk), not only at single-round K
     "BRA_DEC_PERSIST": "0",         # 1 .. 3: persistent step (debug library), prefetch level 0 .. 2
     "BRA_DEC_PERSIST_STOP": "0",    # its diagnostics (bra_qwen_decode_step_persist: stop_after)
     "BRA_SAMPLE_TILES": "1",        # 0: full-scan sampler
@@ -194,7 +195,9 @@ def rollout_weights(model, rows: int = 8):
     # no 32-row form — the folded norm at a hidden size of 6144: those projections keep their bf16 packed image there, a set of its own
     e4m3 = {nm: _streams_e4m3(model, rows, K, normed)
             for nm, K, normed in (("Wqkv", eng.H, True), ("Wo", eng.Nq, False), ("Wgu", eng.H, True), ("Wd", eng.F, False))}
-    key = (model._packed_sig, model._lora_enabled, pack, wide, tuple(e4m3.values()),
+    # BRA_FP8_ANYK=1: a plain projection (o, down) the single-round packer refuses takes the any-K image (ops.dec_pack_weights_fp8_anyk)
+    anyk = {"Wo": _anyk_e4m3(eng.H, eng.Nq), "Wd": _anyk_e4m3(eng.H, eng.F)}
+    key = (model._packed_sig, model._lora_enabled, pack, wide, tuple(e4m3.values()), tuple(anyk.values()),
            None if arena is None or arena.params is None else (arena.step_count, arena.params._version))
     cached = getattr(eng, "_rollout", None)
     if cached is not None and cached[0] == key:
@@ -223,6 +226,10 @@ def rollout_weights(model, rows: int = 8):
             # projection) keeps its bf16 packed image and the step streams both kinds (`fp8_proj`: the names that are e4m3)
             q8 = {nm: ops.dec_pack_weights_fp8(rec[nm], act=(nm == "Wgu"), norm_w=nws[nm], rows=prows)
                   if e4m3[nm] else None for nm in names}
+            for nm in names:
+                # (the step driver sends a plain e4m3 projection without a single-round form to bra_dec_gemm2_fp8_anyk: the same question)
+                if e4m3[nm] and q8[nm] is None and anyk.get(nm):
+                    q8[nm] = ops.dec_pack_weights_fp8_anyk(rec[nm])
             pk = {nm: ops.dec_pack_weights(rec[nm], act=(nm == "Wgu"), norm_w=nws[nm], rows=prows) for nm in names if q8[nm] is None}
             if all(v is not None for v in pk.values()):
                 rec.update({nm + "_p": v for nm, v in pk.items()})
@@ -537,12 +544,22 @@ def fp8_rows32_form_exists(K: int, normed: bool) -> bool:
 def _streams_e4m3(model, rows: int, K: int, normed: bool) -> bool:
     """does a projection of this K (`normed`: its input's norm folded in) stream its e4m3 image in a token loop of `rows` sequences, or its
     bf16 packed image?  An fp8 rollout over packed weights: <= 8 rows wherever the 8-row packer takes the shape; 9 .. 16 rows (BRA_FP8_WIDE)
-    the rows = 16 image, at the single-round K; 17 .. 32 rows (BRA_FP8_ROWS32) the same image where the library has the 32-row form"""
+    the rows = 16 image, at the single-round K; 17 .. 32 rows (BRA_FP8_ROWS32) the same image where the library has the 32-row form.
+    With BRA_FP8_ANYK=1 an un-normed projection (o, down) outside those K streams the any-K image (bra_dec_gemm2_fp8_anyk)"""
     if not (rollout_fp8_enabled(model) and _switch("BRA_DEC_PACK") == "1"):
         return False
+    # (BRA_FP8_ANYK=1: an un-normed projection whose single-round form does not exist streams the any-K image in every row class)
+    anyk = not normed and _anyk_e4m3(model.ensure_packed().H, K)
     if rows <= MAX_DECODE_ROWS:
-        return rows <= 8 or (_switch("BRA_FP8_WIDE") == "1" and fp8_rows32_form_exists(K, False))
-    return rows <= MAX_DECODE_ROWS32 and _switch("BRA_FP8_WIDE") == "1" and _switch("BRA_FP8_ROWS32") == "1" and fp8_rows32_form_exists(K, normed)
+        return rows <= 8 or (_switch("BRA_FP8_WIDE") == "1" and (fp8_rows32_form_exists(K, False) or anyk))
+    return (rows <= MAX_DECODE_ROWS32 and _switch("BRA_FP8_WIDE") == "1" and _switch("BRA_FP8_ROWS32") == "1"
+            and (fp8_rows32_form_exists(K, normed) or anyk))
+
+
+def _anyk_e4m3(N: int, K: int) -> bool:
+    """may a plain (un-normed, bf16-output) [N, K] projection of an fp8 rollout take the any-K e4m3 image where it has no single-round one?
+    Opt-in (BRA_FP8_ANYK=1); the shape rule is the library's (bra_dec_gemm2_fp8_anyk_ok)"""
+    return _switch("BRA_FP8_ANYK") == "1" and ops.dec_gemm2_fp8_anyk_ok(N, K)
 
 
 def _one_loop_ok(model, B: int) -> bool:

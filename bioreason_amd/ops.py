@@ -757,6 +757,38 @@ def dec_gemm2_fp8(x, Wq, scale, ss_in=None, eps=1e-6, res=None, act=False, out_f
     return out, (None if tile_max is not None else ss_out)
 
 
+def dec_gemm2_fp8_anyk_ok(N: int, K: int) -> bool:
+    """does bra_dec_gemm2_fp8_anyk stream an [N, K] e4m3 image?  The library's rule (bra_dec_gemm2_fp8_anyk_ok): N % 16 == 0, K % 64 == 0"""
+    return bool(get_lib()._dll.bra_dec_gemm2_fp8_anyk_ok(int(N), int(K)))
+
+
+def dec_pack_weights_fp8_anyk(W: torch.Tensor):
+    """W [N, K] bf16 -> (q uint8 [N, K], scale fp32 [N]): dec_pack_weights_fp8(rows=16)'s quantiser and order at ANY K % 64 == 0, for
+    dec_gemm2_fp8_anyk (bra_dec_pack_weights_fp8_anyk); None where bra_dec_gemm2_fp8_anyk_ok(N, K) is 0"""
+    N, K = W.shape
+    q = torch.empty((N, K), dtype=torch.uint8, device=W.device)
+    scale = torch.empty((N,), dtype=torch.float32, device=W.device)
+    rc = get_lib().call_rc("bra_dec_pack_weights_fp8_anyk", W, _ld(W), N, K, q, scale, current_stream(W))
+    if rc == -2:
+        return None
+    return q, scale
+
+
+def dec_gemm2_fp8_anyk(x, Wq, scale, res=None, want_ss=False):
+    """the plain decode projection over an any-K e4m3 image (bra_dec_gemm2_fp8_anyk): y = scale[n] (x q^T) (+ res), 1 <= M <= 32 rows;
+    returns (y, ss_out or None) — ss_out [8 | 16 | 32, nss] holds N / 16 partial sums of squares per row; None when unsupported"""
+    M, K = x.shape
+    N = Wq.shape[0]
+    out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    nss_out = (N // 8 + 32) // 32 * 32
+    ss_out = torch.zeros((_stat_rows(M), nss_out), dtype=torch.float32, device=x.device) if want_ss else None
+    rc = get_lib().call_rc("bra_dec_gemm2_fp8_anyk", x, _ld(x), Wq, scale, res, _ld(res) if res is not None else 0, out, _ld(out), ss_out,
+                           nss_out if want_ss else 0, M, N, K, current_stream(x))
+    if rc == -2:
+        return None
+    return out, ss_out
+
+
 def eos_mask(ids32: torch.Tensor, eos_id: int):
     B, C = ids32.shape
     mask = torch.empty((B, C), dtype=torch.int32, device=ids32.device)

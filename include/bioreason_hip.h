@@ -242,6 +242,18 @@ int bra_dec_pack_weights_fp8_rows(const void* W, long ldw, int N, int K, int act
 int bra_dec_gemm2_fp8_rows(const void* x, long ldx, const float* ss_in, int nss_in, float eps, const void* Wq, const float* wscale,
                            const void* res, long ldres, void* out, long ldo, float* ss_out, int nss_out, int M, int N, int K, int act,
                            int out_f32, int norm_folded, int image_rows, void* stream);
+/* fp8 weights at ANY K (k_decgemm8.hip): the plain role of the decode step — no norm, no SwiGLU, bf16 output, optional residual and
+ * statistics: o_proj and down_proj — over an e4m3 image whose K is NOT one register round (Qwen3-4B's down projection, K = 9728; its
+ * o projection, K = 4096, at <= 8 rows; K = 1280, 5120, 8192, 12288, 17408, any short K).  bra_dec_gemm2_fp8_anyk_ok(N, K) states the
+ * rule — N % 16 == 0 and K % 64 == 0 — and packer, launcher and host ask it.  bra_dec_pack_weights_fp8_anyk: bra_dec_pack_weights_fp8_rows'
+ * quantiser and rows = 16 order (16-column tiles, two k-steps per 16-byte chunk) without the single-round check; at a K both take the
+ * bytes are equal.  bra_dec_gemm2_fp8_anyk: y = scale[n] (x q^T) (+ res), 1 <= M <= 32 over that one image, K streamed in rounds; the
+ * order of a row's sum does not depend on M: row r of an M = 32, an M = 16 and an M = r + 1 call are bit-identical.  ss_out: N / 16
+ * partials per row, [8 | 16 | 32][nss_out].  BRA_ERR_UNSUPPORTED for M > 32 and where _ok says 0; nothing is written on refusal. */
+int bra_dec_pack_weights_fp8_anyk(const void* W, long ldw, int N, int K, void* out_q, float* out_scale, void* stream);
+int bra_dec_gemm2_fp8_anyk(const void* x, long ldx, const void* Wq, const float* wscale, const void* res, long ldres, void* out, long ldo,
+                           float* ss_out, int nss_out, int M, int N, int K, void* stream);
+int bra_dec_gemm2_fp8_anyk_ok(int N, int K);
 /* gate/up projection with the SwiGLU in the GEMM epilogue (round 6): act [M, F] = bra_swiglu_fwd(bra_gemm_bf16_nt(A, W [2 F, K] = [gate | up]
  * rows (+ the LoRA rank part A2 B2^T))), bit for bit, without the [M, 2 F] intermediate — no-grad passes only (the backward of a training
  * forward needs gate and up).  BRA_ERR_UNSUPPORTED unless K % 64 == 0, K2 % 64 == 0, F % 128 == 0, M > 16 (callers fall back to the two
