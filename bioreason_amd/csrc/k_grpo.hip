@@ -392,6 +392,145 @@ __global__ __launch_bounds__(256) void logits_process_kernel(float* logits, long
     if (tid == 1 && ban2 >= 0) tr[ban2 >> 4] = tile_max16(lr, ban2 >> 4, V);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The whole token-level processor chain of HF's _get_logits_processor in ONE launch (what runs instead of logits_process_kernel
+// when one of the further controls is on): SequenceBias -> RepetitionPenalty -> NoRepeatNGram -> NoBadWords -> MinNewTokensLength ->
+// SuppressTokens -> SuppressTokensAtBegin, over the GENERATED tokens only (begin_index = 0), one workgroup per row, in place.
+//   A  sequence bias     every DISTINCT last token of the biased sequences belongs to one thread (the host groups the table
+//                        stably by last token: group g = sequences grp_off[g] .. grp_off[g+1]-1).  The thread forms HF's bias[tok]
+//                        = 0 + b_1 + b_2 + ... in the caller's order and in fp32 (a sequence that does not match adds 0.0), then
+//                        stores l + bias: the bits HF's `scores + bias` leaves.  A sequence of L tokens matches when its first
+//                        L - 1 tokens equal hist[t-L+1 .. t-1]; L = 1 always matches, L > 1 only from t >= L on (HF skips
+//                        sequences longer than input_ids, so L - 1 tokens of history are NOT enough).  A bias whose BIT IMAGE is
+//                        -inf is never added: the thread stores the -inf constant (the device build's arithmetic flags are free
+//                        to fold an addition of infinity differently from the host executor).
+//   B  repetition penalty  read - barrier - write as in logits_process_kernel, over the biased values: (l + b) may have changed sign.
+//   C  the -inf writers  after a barrier, idempotent, in any order: every window j <= t - n with hist[j .. j+n-2] == hist[t-n+1 ..
+//                        t-1] bans hist[j+n-1] (nothing while t < n; n = 1 bans every generated token); every matching bad word
+//                        bans its last token; the EOS ids while t < min_new_tokens; the suppress list; the begin list at t == 0.
+//                        List ids outside [0, V) have no effect (HF: isin over the vocabulary).
+//   D  tile maxima       after a barrier the tile of EVERY candidate column (matched or not: recomputing is idempotent) is
+//                        recomputed from the stored logits — a bias can raise a tile's maximum, a ban can remove it.
+// Nothing is carried from step to step and t comes from the device word or the launch argument: the launch is the same issued
+// eagerly, replayed from a graph or after a counter reset.  Table addresses are clamped, not branched around.
+constexpr int kSeqMax = 1024;                     // biased sequences + bad words
+constexpr int kSeqTokMax = 4096;                  // their tokens, flattened
+constexpr int kSuppressMax = 1024;                // entries of each suppress list
+constexpr int kNgramMax = 32;                     // no_repeat_ngram_size
+constexpr uint32_t kNegInfBits = 0xff800000u;
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// sequence s = seq_tok[o0 .. o1-1] would be completed by its last token at step t
+__device__ __forceinline__ bool seq_matches(const int* seq_tok, int o0, int o1, int tok_last, const int* hr, int t) {
+    const int L = o1 - o0;
+    if (L < 1 || (L > 1 && t < L)) return false;                 // (t <= hist_cols: every index below is inside the history)
+    int eq = 1;
+    for (int i = 0; i < L - 1; ++i) eq &= (int)(hr[t - (L - 1) + i] == seq_tok[clampi(o0 + i, 0, tok_last)]);
+    return eq != 0;
+}
+
+__global__ __launch_bounds__(256) void logits_process_ext_kernel(float* logits, long ldl, int V, const int* hist, long ldh, int hist_cols,
+                                                                 const int* step_ptr, int step_arg, float penalty, int min_new,
+                                                                 int eos_id, int eos_id2, int ngram, const int* seq_tok,
+                                                                 const int* seq_off, const float* seq_bias, int n_bias, int n_bad,
+                                                                 int n_tok, const int* grp_off, int n_grp, const int* sup, int n_sup,
+                                                                 const int* bsup, int n_bsup, const uint8_t* finished, float* tmax,
+                                                                 long ldm) {
+    __shared__ float s_orig[kHistMax];
+    const int row = (int)blockIdx.x, tid = (int)threadIdx.x;
+    if (finished && finished[row]) return;        // (uniform over the workgroup: nobody reaches a barrier)
+    int step = step_ptr ? step_ptr[0] : step_arg;
+    step = step < 0 ? 0 : step;                   // what min_new_tokens and the begin list go by (they read no history)
+    const int t = step > hist_cols ? hist_cols : step;          // never past the history the caller handed in
+    int n = penalty != 1.f ? t : 0;
+    n = n > kHistMax ? kHistMax : n;
+    float* lr = logits + (long)row * ldl;
+    const int* hr = hist + (long)row * ldh;
+    const float ninf = __builtin_bit_cast(float, kNegInfBits);
+    const int tok_last = n_tok - 1, seq_last = n_bias + n_bad - 1;
+    const bool ban = step < min_new;
+    const int ban1 = (ban && eos_id >= 0 && eos_id < V) ? eos_id : -1, ban2 = (ban && eos_id2 >= 0 && eos_id2 < V) ? eos_id2 : -1;
+    // --- A: sequence bias
+    for (int g = tid; g < n_grp; g += 256) {
+#pragma clang fp reassociate(off)
+        const int s0 = clampi(grp_off[g], 0, n_bias - 1), s1 = clampi(grp_off[g + 1], s0 + 1, n_bias);
+        const int tok = seq_tok[clampi(seq_off[s0 + 1] - 1, 0, tok_last)];
+        float acc = 0.f;
+        bool to_ninf = false;
+        for (int s = s0; s < s1; ++s) {
+            const int o0 = seq_off[s], o1 = seq_off[s + 1];
+            const float b = seq_bias[s];
+            const bool is_ninf = __builtin_bit_cast(uint32_t, b) == kNegInfBits;
+            const bool m = seq_tok[clampi(o1 - 1, 0, tok_last)] == tok && seq_matches(seq_tok, o0, o1, tok_last, hr, t);
+            to_ninf = to_ninf || (m && is_ninf);
+            acc = acc + ((m && !is_ninf) ? b : 0.f);
+        }
+        if (tok >= 0 && tok < V) {
+            const float l = lr[tok];
+            lr[tok] = to_ninf ? ninf : l + acc;
+        }
+    }
+    if (n_grp > 0) __syncthreads();
+    // --- B: repetition penalty over the biased values
+    for (int j = tid; j < n; j += 256) {
+        const int id = hr[j];
+        s_orig[j] = (id >= 0 && id < V) ? lr[id] : 0.f;
+    }
+    __syncthreads();
+    for (int j = tid; j < n; j += 256) {
+        const int id = hr[j];
+        if (id < 0 || id >= V) continue;
+        const float l = s_orig[j];
+        lr[id] = l < 0.f ? l * penalty : l / penalty;
+    }
+    __syncthreads();
+    // --- C: the -inf writers
+    const int nwin = (ngram > 0 && t >= ngram) ? t - ngram + 1 : 0;
+    for (int j = tid; j < nwin; j += 256) {
+        int eq = 1;
+        for (int i = 0; i < ngram - 1; ++i) eq &= (int)(hr[j + i] == hr[t - ngram + 1 + i]);
+        const int id = hr[j + ngram - 1];
+        if (eq && id >= 0 && id < V) lr[id] = ninf;
+    }
+    for (int s = n_bias + tid; s <= seq_last; s += 256) {
+        const int o0 = seq_off[s], o1 = seq_off[s + 1];
+        const int id = seq_tok[clampi(o1 - 1, 0, tok_last)];
+        if (seq_matches(seq_tok, o0, o1, tok_last, hr, t) && id >= 0 && id < V) lr[id] = ninf;
+    }
+    if (tid == 0 && ban1 >= 0) lr[ban1] = ninf;
+    if (tid == 1 && ban2 >= 0) lr[ban2] = ninf;
+    const int nb = step == 0 ? n_bsup : 0;
+    for (int j = tid; j < n_sup + nb; j += 256) {
+        const int id = j < n_sup ? sup[j] : bsup[j - n_sup];
+        if (id >= 0 && id < V) lr[id] = ninf;
+    }
+    if (!tmax) return;
+    __syncthreads();
+    // --- D: the tile of every candidate column from what is stored
+    float* tr = tmax + (long)row * ldm;
+    for (int g = tid; g < n_grp; g += 256) {
+        const int s0 = clampi(grp_off[g], 0, n_bias - 1);
+        const int id = seq_tok[clampi(seq_off[s0 + 1] - 1, 0, tok_last)];
+        if (id >= 0 && id < V) tr[id >> 4] = tile_max16(lr, id >> 4, V);
+    }
+    const int nh = (n > 0 || nwin > 0) ? t : 0;   // (every history entry: the penalised ids and the ends of the windows)
+    for (int j = tid; j < nh; j += 256) {
+        const int id = hr[j];
+        if (id >= 0 && id < V) tr[id >> 4] = tile_max16(lr, id >> 4, V);
+    }
+    for (int s = n_bias + tid; s <= seq_last; s += 256) {
+        const int id = seq_tok[clampi(seq_off[s + 1] - 1, 0, tok_last)];
+        if (id >= 0 && id < V) tr[id >> 4] = tile_max16(lr, id >> 4, V);
+    }
+    if (tid == 0 && ban1 >= 0) tr[ban1 >> 4] = tile_max16(lr, ban1 >> 4, V);
+    if (tid == 1 && ban2 >= 0) tr[ban2 >> 4] = tile_max16(lr, ban2 >> 4, V);
+    for (int j = tid; j < n_sup + nb; j += 256) {
+        const int id = j < n_sup ? sup[j] : bsup[j - n_sup];
+        if (id >= 0 && id < V) tr[id >> 4] = tile_max16(lr, id >> 4, V);
+    }
+}
+
 // NL = list entries per lane in stage 2a (nsl * k <= 64 * NL), NU = gathered logits per lane (16 k <= 64 * NU)
 template <int NL, int NU>
 __global__ __launch_bounds__(64) void sample_tiles_kernel(const float* logits, long ldl, int V, const float* cand_v, const int* cand_i,
@@ -1048,6 +1187,43 @@ extern "C" int bra_logits_process(float* logits, long ldl, int B, int V, const i
     }
     BRA_LAUNCH(logits_process_kernel, dim3(B), dim3(256), 0, stream, logits, ldl, V, hist, ldh, hist_cols, step_ptr, step, penalty,
                min_new_tokens, eos_id, eos_id2, (const uint8_t*)finished, tmax, ldm);
+    return BRA_LAUNCH_STATUS();
+}
+
+// bra_logits_process + sequence bias, no-repeat n-gram, bad words and the two suppress lists, in HF's order and in one launch — see
+// logits_process_ext_kernel.  Sequence table: sequences 0 .. n_bias-1 are the biased ones, grouped by last token (grp_off [n_grp + 1]
+// indexes them; within a group the caller's order), n_bias .. n_bias+n_bad-1 the bad words; seq_off [n_bias + n_bad + 1] delimits
+// their tokens in seq_tok [n_tok].  No launch where every control is off.  BRA_ERR_UNSUPPORTED beyond the fixed limits: 8192 history
+// entries under a penalty or an n-gram ban, n-grams of 32, 1024 sequences, 4096 sequence tokens, 1024 ids per suppress list.
+extern "C" int bra_logits_process_ext(float* logits, long ldl, int B, int V, const int* hist, long ldh, int hist_cols,
+                                      const int* step_ptr, int step, float penalty, int min_new_tokens, int eos_id, int eos_id2,
+                                      int no_repeat_ngram, const int* seq_tok, const int* seq_off, const float* seq_bias, int n_bias,
+                                      int n_bad, int n_tok, const int* grp_off, int n_grp, const int* suppress, int n_suppress,
+                                      const int* begin_suppress, int n_begin_suppress, const void* finished, float* tmax, long ldm,
+                                      void* stream) {
+    if (B == 0) return 0;
+    if (!(penalty > 0.f) || min_new_tokens < 0 || hist_cols < 0 || V <= 0 || no_repeat_ngram < 0 || n_bias < 0 || n_bad < 0 ||
+        n_tok < 0 || n_grp < 0 || n_suppress < 0 || n_begin_suppress < 0)
+        return BRA_ERR_ARG;
+    const long n_seq = (long)n_bias + n_bad;
+    if (n_tok < n_seq || (n_seq == 0 && n_tok != 0) || n_grp > n_bias || (n_grp == 0) != (n_bias == 0)) return BRA_ERR_ARG;
+    if ((n_seq > 0 && (!seq_tok || !seq_off)) || (n_bias > 0 && (!seq_bias || !grp_off)) || (n_suppress > 0 && !suppress) ||
+        (n_begin_suppress > 0 && !begin_suppress))
+        return BRA_ERR_ARG;
+    if (penalty == 1.f && min_new_tokens == 0 && no_repeat_ngram == 0 && n_seq == 0 && n_suppress == 0 && n_begin_suppress == 0)
+        return 0;
+    if (!step_ptr && step < 0) return BRA_ERR_ARG;
+    if (!logits || (tmax && ldm < (V + 15) / 16)) return BRA_ERR_ARG;
+    if (penalty != 1.f || no_repeat_ngram > 0 || n_tok > n_seq) {           // the controls that read the history
+        if ((!hist && hist_cols > 0) || (!step_ptr && step > hist_cols)) return BRA_ERR_ARG;
+        if ((penalty != 1.f || no_repeat_ngram > 0) && (step_ptr ? hist_cols : step) > kHistMax) return BRA_ERR_UNSUPPORTED;
+    }
+    if (no_repeat_ngram > kNgramMax || n_seq > kSeqMax || n_tok > kSeqTokMax || n_suppress > kSuppressMax ||
+        n_begin_suppress > kSuppressMax)
+        return BRA_ERR_UNSUPPORTED;
+    BRA_LAUNCH(logits_process_ext_kernel, dim3(B), dim3(256), 0, stream, logits, ldl, V, hist, ldh, hist_cols, step_ptr, step, penalty,
+               min_new_tokens, eos_id, eos_id2, no_repeat_ngram, seq_tok, seq_off, seq_bias, n_bias, n_bad, n_tok, grp_off, n_grp,
+               suppress, n_suppress, begin_suppress, n_begin_suppress, (const uint8_t*)finished, tmax, ldm);
     return BRA_LAUNCH_STATUS();
 }
 

@@ -353,7 +353,8 @@ class DNALLMModel(nn.Module):
         kw = {}
         # the HF generation keywords this path honours (INTEGRATION.md lists them); any other HF keyword is still ignored
         for k in ("max_new_tokens", "do_sample", "temperature", "top_k", "top_p", "eos_token_id", "pad_token_id",
-                  "repetition_penalty", "min_new_tokens", "min_p"):
+                  "repetition_penalty", "min_new_tokens", "min_p", "no_repeat_ngram_size", "bad_words_ids", "suppress_tokens",
+                  "begin_suppress_tokens", "sequence_bias"):
             if gc is not None and getattr(gc, k, None) is not None:
                 kw[k] = getattr(gc, k)
             if k in generation_kwargs and generation_kwargs[k] is not None:

@@ -623,6 +623,68 @@ def _eos_ids(eos_token_id, pad_token_id):
     return eos, eos2, pad
 
 
+def _is_id(t) -> bool:
+    import numpy as np
+    return isinstance(t, (int, np.integer)) and not isinstance(t, bool)
+
+
+def _validated_controls(no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens, sequence_bias, eos_ids):
+    """The five further HF processors' arguments, validated as HF's classes validate them (TF:generation/logits_process.py:
+    NoRepeatNGram, NoBadWords, SuppressTokens, SuppressTokensAtBegin, SequenceBias) -> the keywords of ops.ProcessorTables, or None
+    when all five are off.  Ours: a bias must be finite or -inf (+inf and NaN have no sensible sum)."""
+    import math
+    n = no_repeat_ngram_size
+    if n is not None and (not _is_id(n) or n < 0):
+        raise ValueError(f"`no_repeat_ngram_size` has to be a non-negative integer (0: off), but is {n!r}")
+    bad = None
+    if bad_words_ids is not None:
+        if not isinstance(bad_words_ids, list) or len(bad_words_ids) == 0:
+            raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bad_words_ids!r}.")
+        if any(not isinstance(w, list) for w in bad_words_ids):
+            raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {bad_words_ids!r}.")
+        if any(len(w) == 0 or any(not _is_id(t) or t < 0 for t in w) for w in bad_words_ids):
+            raise ValueError(f"Each list in `bad_words_ids` has to be a non-empty list of positive integers, but is {bad_words_ids!r}.")
+        # HF drops the words that are exactly [eos]: banning them would keep a row from ever ending
+        bad = [w for w in bad_words_ids if not (len(w) == 1 and w[0] in [e for e in eos_ids if e >= 0])]
+    bias = None
+    if sequence_bias is not None:
+        sb = sequence_bias
+        if not isinstance(sb, (dict, list)) or len(sb) == 0:
+            raise ValueError(f"`sequence_bias` has to be a non-empty dictionary, or non-empty list of lists but is {sb!r}.")
+        if isinstance(sb, list):
+            # (HF asks ids > 0 in the list form and >= 0 in the dict form; so does this)
+            if any(not isinstance(e, (list, tuple)) or len(e) != 2 or not isinstance(e[0], list) or len(e[0]) == 0
+                   or any(not _is_id(t) or t <= 0 for t in e[0]) or not isinstance(e[1], float) for e in sb):
+                raise ValueError("Each element in `sequence_bias` has to be a non-empty list of lists of positive integers and float, "
+                                 f"but is {sb!r}.")
+            sb = {tuple(e[0]): e[1] for e in sb}
+        if any(not isinstance(k, tuple) for k in sb):
+            raise ValueError(f"`sequence_bias` has to be a dict with tuples as keys, but is {sb!r}.")
+        if any(len(k) == 0 or any(not _is_id(t) or t < 0 for t in k) for k in sb):
+            raise ValueError(f"Each key in `sequence_bias` has to be a non-empty tuple of positive integers, but is {sb!r}.")
+        if any(not isinstance(b, float) for b in sb.values()):
+            raise ValueError(f"`sequence_bias` has to be a dict with floats as values, but is {sb!r}.")
+        if any(math.isnan(b) or b == math.inf for b in sb.values()):
+            raise ValueError(f"Each bias in `sequence_bias` has to be finite or -inf, but is {sb!r}.")
+        bias = sb
+    lists = []
+    for name, ids in (("suppress_tokens", suppress_tokens), ("begin_suppress_tokens", begin_suppress_tokens)):
+        if ids is None:
+            lists.append(None)
+            continue
+        if isinstance(ids, torch.Tensor):
+            ids = ids.tolist()
+        if isinstance(ids, (str, bytes)) or not hasattr(ids, "__iter__"):
+            raise ValueError(f"`{name}` has to be a list of integers, but is {ids!r}")
+        ids = list(ids)
+        if any(not _is_id(t) for t in ids):
+            raise ValueError(f"`{name}` has to be a list of integers, but is {ids!r}")
+        lists.append(ids)
+    if not (n or bad or bias or lists[0] or lists[1]):
+        return None
+    return dict(ngram=int(n or 0), sequence_bias=bias, bad_words=bad, suppress=lists[0], begin_suppress=lists[1])
+
+
 def _prompt_pass(model, inputs_embeds, attention_mask, am, pos_prompt, prompt_alias, shared_grp, max_new_tokens: int):
     """The prompt through the stack, once per DISTINCT prompt -> (last hidden rows [B, H], per-sequence KVCache or None,
     SharedDecodeState or None, its prompt mask or None).  `shared_grp` (R, copies): the shared-prefix step decodes — the prompt K / V^T
@@ -699,7 +761,9 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
              decode_impl: str = "fused", prompt_alias=None, use_graph: Optional[bool] = None,
              shared_prefix_decode: bool = True, profile: Optional[dict] = None, loop_events: Optional[list] = None,
              eos_schedule: Optional[torch.Tensor] = None, trace_logits: Optional[list] = None,
-             repetition_penalty: float = 1.0, min_new_tokens: int = 0, min_p: Optional[float] = None) -> torch.Tensor:
+             repetition_penalty: float = 1.0, min_new_tokens: int = 0, min_p: Optional[float] = None,
+             no_repeat_ngram_size: int = 0, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None,
+             sequence_bias=None) -> torch.Tensor:
     """`force_tokens` [B, max_new_tokens] (optional): teacher forcing — the model's own choice is still recorded
     in the output, but the given token is fed back (used to compare decodes position by position).
     `use_graph`: True = sample + decode step + counter update are captured once in a hipGraph and replayed per token
@@ -715,7 +779,12 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
     MinPLogitsWarper in HF's order (penalty -> min length -> temperature -> top-k -> top-p -> min-p).  The penalty runs over the
     GENERATED tokens only — what HF does for a generate() call with inputs_embeds and no input_ids, as the reference makes it
     (under `force_tokens`: over the tokens fed back).  The first two are one launch in front of the sampler (ops.logits_process),
-    issued only when one of them is on; min_p lives in the samplers and is ignored when greedy (HF runs no warper then)."""
+    issued only when one of them is on; min_p lives in the samplers and is ignored when greedy (HF runs no warper then).
+    `sequence_bias`, `no_repeat_ngram_size`, `bad_words_ids`, `suppress_tokens`, `begin_suppress_tokens`: HF's processors of the
+    same names, validated as HF validates them, over the generated tokens only (begin_index 0) and in HF's order: sequence bias ->
+    penalty -> n-gram -> bad words -> min length -> suppress -> begin suppress.  One addition: a bias must be finite or -inf.  With one
+    of them on, ops.logits_process_ext runs the whole chain in one launch INSTEAD of ops.logits_process; its fixed limits
+    (ops.ProcessorTables) are a ValueError here, before any launch."""
     _call_kw = dict(locals())                      # every argument of this call, by name (forwarded whole by the row-chunk path)
     # validation as HF's processors (TF:generation/logits_process.py), plus the bound of the kernel's history staging
     if isinstance(repetition_penalty, bool) or not isinstance(repetition_penalty, (int, float)) or not repetition_penalty > 0:
@@ -729,9 +798,22 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
                          f"bra_logits_process), but max_new_tokens is {max_new_tokens}")
     process = repetition_penalty != 1.0 or min_new_tokens > 0
     min_p_dev = float(min_p) if (do_sample and min_p is not None) else 0.0
+    ctl = _validated_controls(no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens, sequence_bias,
+                              _eos_ids(eos_token_id, pad_token_id)[:2])
     eng = model.ensure_packed()
     B, P, H = inputs_embeds.shape
     dev = inputs_embeds.device
+    # the device tables of the further processors, once per call and before any launch (None: all five are off — the loop then issues
+    # exactly what it issued before they existed)
+    tables = None
+    if ctl is not None:
+        tables = ops.ProcessorTables(eng.V, dev, **ctl)
+        over = tables.over_capacity()
+        if over is not None:
+            raise ValueError(f"bra_logits_process_ext serves {over}")
+        if tables.ngram and max_new_tokens > tables.HIST_MAX:
+            raise ValueError(f"`no_repeat_ngram_size` is supported for max_new_tokens <= {tables.HIST_MAX} (the history one launch of "
+                             f"bra_logits_process_ext scans), but max_new_tokens is {max_new_tokens}")
     max_rows = MAX_DECODE_ROWS
     if B > MAX_DECODE_ROWS and native_step and decode_impl == "fused" and decode_rows_limit() > MAX_DECODE_ROWS \
             and _one_loop_ok(model, min(B, MAX_DECODE_ROWS32)):
@@ -824,9 +906,19 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
     counters_at = [0]                       # the step index the device-side counters (step_t, len_t, next_pos) hold
     # history of the repetition penalty: the [B, max_new_tokens] matrix the sampler fills (columns 0 .. t-1 at step t), or — under
     # teacher forcing — the tokens fed back, as HF's input_ids would hold them
+    # (the n-gram ban and multi-token sequences read the same history)
     hist = None
-    if process:
+    if process or (tables is not None and (tables.ngram or tables.multi_token)):
         hist = tokens if force_tokens is None else force_tokens.to(device=dev, dtype=torch.int32).contiguous()
+
+    fin_ = finished if eos >= 0 else None
+
+    def process_(st, tm):
+        """the processors in front of the sampler: ONE launch, none when every control is off"""
+        if tables is not None:
+            ops.logits_process_ext(logits, hist, st, tables, repetition_penalty, min_new_tokens, eos, eos2, fin_, tm)
+        elif process:
+            ops.logits_process(logits, hist, st, repetition_penalty, min_new_tokens, eos, eos2, fin_, tm)
 
     def sample_(t_host: Optional[int] = None):
         """the draw of step t.  `t_host` given: launch-by-launch issue (the index travels as an argument where the kernels take it)"""
@@ -837,8 +929,7 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
             st = t_host if host_step else step_t
             if eos_schedule is not None:
                 ops.force_token_tiles(logits, eos, st, eos_schedule, tmax)
-            if process:                     # (after the schedule, which stands for the model's own logits)
-                ops.logits_process(logits, hist, st, repetition_penalty, min_new_tokens, eos, eos2, fin, tmax)
+            process_(st, tmax)              # (after the schedule, which stands for the model's own logits)
             ops.sample_tiles(logits, tmax, temperature, top_k, top_p, do_sample, seed, st, fin, pad, cur, None, eos_id=eos,
                              eos_id2=eos2, tokens_out=tokens, ws=sample_ws, embed=emb,
                              advance=(pos0, next_pos, rope_args[0], rope_args[1], rope_args[2], rope_args[3]) if host_step else None,
@@ -846,8 +937,7 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
             return
         if eos_schedule is not None:
             ops.force_token(logits, eos, step_t, eos_schedule)
-        if process:
-            ops.logits_process(logits, hist, step_t, repetition_penalty, min_new_tokens, eos, eos2, fin, None)
+        process_(step_t, None)
         ops.sample(logits, temperature, top_k, top_p, do_sample, seed, step_t, fin, pad,
                    cur, None, eos_id=eos, eos_id2=eos2, tokens_out=tokens, ws=sample_ws, embed=emb, min_p=min_p_dev)
 

@@ -618,6 +618,79 @@ def logits_process(logits: torch.Tensor, hist: Optional[torch.Tensor], step, pen
     return logits
 
 
+class ProcessorTables:
+    """Device tables of `logits_process_ext`, built once per generate() call.
+    `sequence_bias`: {tuple of ids: bias} (bias finite or -inf); `bad_words`: list of lists of ids (the caller has dropped [eos]);
+    `suppress`, `begin_suppress`: iterables of ids (ids outside [0, V) have no effect, as HF's isin has none); `ngram`: HF's
+    no_repeat_ngram_size (0 = off).  A sequence token >= V is a ValueError, as HF raises on first use.
+    The biased sequences are grouped STABLY by last token — a single-token sequence first, as HF adds length-1 biases first, the
+    longer ones in the dict's order — so that the one thread that owns a token adds the biases in HF's order."""
+    HIST_MAX, NGRAM_MAX, SEQ_MAX, SEQ_TOK_MAX, SUPPRESS_MAX = 8192, 32, 1024, 4096, 1024        # k_grpo.hip
+
+    def __init__(self, V: int, device, ngram: int = 0, sequence_bias=None, bad_words=None, suppress=None, begin_suppress=None):
+        bias = [(tuple(int(t) for t in k), float(b)) for k, b in (sequence_bias or {}).items()]
+        bad = [tuple(int(t) for t in w) for w in (bad_words or [])]
+        out = [t for k, _ in bias for t in k if t >= V] + [t for w in bad for t in w if t >= V]
+        if out:
+            raise ValueError(f"The model vocabulary size is {V}, but the following tokens were being biased: {out}")
+        groups = {}
+        for k, b in bias:
+            groups.setdefault(k[-1], []).append((k, b))
+        seqs, grp_off = [], [0]
+        for members in groups.values():
+            members.sort(key=lambda kb: len(kb[0]) != 1)          # stable: the single-token sequence first, the rest as given
+            seqs += members
+            grp_off.append(len(seqs))
+        self.ngram, self.n_bias, self.n_bad, self.n_grp = int(ngram or 0), len(seqs), len(bad), len(groups)
+        toks = [t for k, _ in seqs for t in k] + [t for w in bad for t in w]
+        off = [0]
+        for k in [k for k, _ in seqs] + bad:
+            off.append(off[-1] + len(k))
+        self.n_tok = len(toks)
+        self.multi_token = self.n_tok > self.n_bias + self.n_bad
+        sup, bsup = [int(t) for t in (suppress or [])], [int(t) for t in (begin_suppress or [])]
+        self.n_sup, self.n_bsup = len(sup), len(bsup)
+
+        def dev_(vals, dtype=torch.int32):
+            return torch.tensor(vals, dtype=dtype, device=device) if vals else None
+        self.seq_tok, self.seq_off = dev_(toks), dev_(off) if toks else None
+        self.seq_bias, self.grp_off = dev_([b for _, b in seqs], torch.float32), dev_(grp_off) if seqs else None
+        self.sup, self.bsup = dev_(sup), dev_(bsup)
+
+    @property
+    def on(self) -> bool:
+        return bool(self.ngram or self.n_bias or self.n_bad or self.n_sup or self.n_bsup)
+
+    def over_capacity(self) -> Optional[str]:
+        """the limit of bra_logits_process_ext these tables exceed, in words (None: they fit)"""
+        if self.ngram > self.NGRAM_MAX:
+            return f"no_repeat_ngram_size <= {self.NGRAM_MAX}"
+        if self.n_bias + self.n_bad > self.SEQ_MAX:
+            return f"at most {self.SEQ_MAX} sequences in sequence_bias and bad_words_ids together"
+        if self.n_tok > self.SEQ_TOK_MAX:
+            return f"at most {self.SEQ_TOK_MAX} tokens in the sequences of sequence_bias and bad_words_ids together"
+        if max(self.n_sup, self.n_bsup) > self.SUPPRESS_MAX:
+            return f"at most {self.SUPPRESS_MAX} ids in suppress_tokens and in begin_suppress_tokens"
+        return None
+
+
+def logits_process_ext(logits: torch.Tensor, hist: Optional[torch.Tensor], step, tables: ProcessorTables, penalty: float = 1.0,
+                       min_new_tokens: int = 0, eos_id: int = -1, eos_id2: int = -1, finished: Optional[torch.Tensor] = None,
+                       tmax: Optional[torch.Tensor] = None):
+    """`logits_process` with HF's sequence bias, no-repeat n-gram, bad words and the two suppress lists (`tables`), in HF's order
+    (bias -> penalty -> n-gram -> bad words -> min_new_tokens -> suppress -> begin suppress) and in one launch; `hist`, `step`,
+    `finished`, `tmax` as there.  Raises KernelError (BRA_ERR_UNSUPPORTED) beyond the limits ProcessorTables names."""
+    B, V = logits.shape
+    assert logits.dtype == torch.float32 and (hist is None or (hist.dtype == torch.int32 and hist.stride(1) == 1 and hist.shape[0] == B))
+    step_ptr, step_i = (step, 0) if isinstance(step, torch.Tensor) else (None, int(step))
+    tb = tables
+    get_lib().call("bra_logits_process_ext", logits, _ld(logits), B, V, hist, hist.stride(0) if hist is not None else 0,
+                   hist.shape[1] if hist is not None else 0, step_ptr, step_i, float(penalty), int(min_new_tokens), int(eos_id),
+                   int(eos_id2), tb.ngram, tb.seq_tok, tb.seq_off, tb.seq_bias, tb.n_bias, tb.n_bad, tb.n_tok, tb.grp_off, tb.n_grp,
+                   tb.sup, tb.n_sup, tb.bsup, tb.n_bsup, finished, tmax, _ld(tmax) if tmax is not None else 0, current_stream(logits))
+    return logits
+
+
 def force_token_tiles(logits: torch.Tensor, token: int, step, at: torch.Tensor, tmax: Optional[torch.Tensor]):
     """`force_token` that keeps the tile maxima consistent; `step`: device int32 [1] or python int"""
     B, V = logits.shape

@@ -47,6 +47,9 @@ class GRPOConfig:
     # the behaviour policy differs from the policy the ratio is taken against.
     repetition_penalty: float = 1.0
     min_p: Optional[float] = None
+    no_repeat_ngram_size: int = 0
+    bad_words_ids: Optional[list] = None
+    suppress_tokens: Optional[list] = None
     beta: float = 0.04
     epsilon: float = 0.2
     epsilon_high: Optional[float] = None
@@ -351,6 +354,8 @@ class GRPOStepRunner(_DataParallelStep):
         completion_ids = m.generate(input_ids=prompt_ids, attention_mask=prompt_mask, **mm,
                                     max_new_tokens=c.max_completion_length, do_sample=True, temperature=c.temperature,
                                     top_k=c.top_k, top_p=c.top_p, repetition_penalty=c.repetition_penalty, min_p=c.min_p,
+                                    no_repeat_ngram_size=c.no_repeat_ngram_size, bad_words_ids=c.bad_words_ids,
+                                    suppress_tokens=c.suppress_tokens,
                                     eos_token_id=c.eos_token_id, pad_token_id=c.pad_token_id,
                                     seed=c.seed + 1000003 * self.step_idx + self.rank, return_full_length=sched is None,
                                     prompt_alias=batch.get("prompt_alias"), use_graph=c.rollout_graph,

@@ -458,6 +458,32 @@ int bra_force_token_tiles(float* logits, long ldl, int B, int V, int token, cons
 int bra_logits_process(float* logits, long ldl, int B, int V, const int* hist, long ldh, int hist_cols, const int* step_ptr, int step,
                        float penalty, int min_new_tokens, int eos_id, int eos_id2, const void* finished, float* tmax, long ldm,
                        void* stream);
+/* bra_logits_process with the rest of HF's token-level processors, in HF's order and in ONE launch (issued INSTEAD of
+ * bra_logits_process when one of these controls is on): SequenceBiasLogitsProcessor -> RepetitionPenaltyLogitsProcessor ->
+ * NoRepeatNGramLogitsProcessor -> NoBadWordsLogitsProcessor -> MinNewTokensLengthLogitsProcessor -> SuppressTokensLogitsProcessor ->
+ * SuppressTokensAtBeginLogitsProcessor (begin_index 0), all over the GENERATED tokens hist[b][0 .. t-1].
+ *   sequence table   seq_off [n_bias + n_bad + 1] delimits the tokens of every sequence in seq_tok [n_tok].  Sequences 0 .. n_bias-1
+ *                    carry seq_bias [n_bias] (finite or -inf) and are GROUPED by last token: group g is sequences grp_off[g] ..
+ *                    grp_off[g+1]-1 (grp_off [n_grp + 1]), each distinct last token in exactly one group, the caller's order kept
+ *                    inside a group (a single-token sequence first, as HF adds it first).  logit[last] += the fp32 sum, in that
+ *                    order, of the biases of the group's matching sequences; a matching -inf stores -inf.  Sequences n_bias ..
+ *                    n_bias+n_bad-1 are the bad words: a match stores -inf (after the penalty, as HF orders them).
+ *   matching         a sequence of L tokens matches when its first L - 1 tokens equal hist[t-L+1 .. t-1].  L = 1 always matches;
+ *                    L > 1 acts only from t >= L on, NOT from L - 1 (HF skips sequences longer than its input_ids).
+ *   no_repeat_ngram  n > 0: nothing while t < n; otherwise every window j with hist[j .. j+n-2] == hist[t-n+1 .. t-1] stores -inf at
+ *                    hist[j+n-1] (n = 1: at every generated token).
+ *   suppress [n_suppress] at every step, begin_suppress [n_begin_suppress] at t == 0: -inf; ids outside [0, V) have no effect.
+ * The penalty runs over the biased values.  tmax, finished, step_ptr / step, hist as for bra_logits_process, except that hist may be
+ * null (hist_cols 0) while no penalty, no n-gram ban and no multi-token sequence is on: min_new_tokens and the begin list go by the
+ * step itself, not by the step clamped to hist_cols.  Sequence tokens outside
+ * [0, V) never match a column (the host refuses them, as HF does).  No launch when every control is off.
+ * BRA_ERR_UNSUPPORTED (nothing written): more than 8192 history entries under a penalty or an n-gram ban, no_repeat_ngram > 32, more
+ * than 1024 sequences or 4096 sequence tokens, more than 1024 ids in a suppress list. */
+int bra_logits_process_ext(float* logits, long ldl, int B, int V, const int* hist, long ldh, int hist_cols, const int* step_ptr, int step,
+                           float penalty, int min_new_tokens, int eos_id, int eos_id2, int no_repeat_ngram, const int* seq_tok,
+                           const int* seq_off, const float* seq_bias, int n_bias, int n_bad, int n_tok, const int* grp_off, int n_grp,
+                           const int* suppress, int n_suppress, const int* begin_suppress, int n_begin_suppress, const void* finished,
+                           float* tmax, long ldm, void* stream);
 /* counters of the replayed token loop: pos[0..n) += 1, a[0] += 1, b[0] += 1 (a, b optional); when `rope_rows` is given, also
  * rope_rows[i][0..hd/2) = cosT[pos[i]], [hd/2..hd) = sinT[pos[i]] for the NEW positions (see bra_rope_rows) */
 int bra_advance_counters(int* pos, int n, int* a, int* b, const float* cosT, const float* sinT, int hd, float* rope_rows,
