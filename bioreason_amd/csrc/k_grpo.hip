@@ -990,6 +990,90 @@ __global__ __launch_bounds__(64) void force_token_kernel(float* logits, long ldl
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Log-probability of the token a draw recorded, under the step's OWN logits: out[b, step] = logits[b, tok] - logsumexp_v(logits[b, :])
+// — the full vocabulary, temperature 1, whatever the warpers did (what _get_per_token_logps computes on the training side,
+// grpo_trainer.py:492-506).  Issued after the draw and before the decode step overwrites the logits, so the B V floats come from L2.
+//   stage 1  kLpSlices vocabulary slices per row (one workgroup per row would leave at most 32 CUs streaming): every thread
+//            requests its whole share of the slice with 16-byte loads up front (<= 8 per thread at V = 262 144), then — over
+//            registers — the slice maximum M (exact) and S = sum exp(x - M): no online rescaling, two block reductions.
+//   stage 2  one wave per row: the maximum of the slice maxima, sum_s S_s exp(M_s - M) by a wave tree, lane 0 subtracts.
+// A slice is ceil(V / kLpSlices) columns rounded up to 4; thread t owns the 4-column groups t, t + 256, ... of its slice.  Partition
+// and merge order depend on V alone — not on B, the row's address or where the step index came from — so row b's value is the same
+// bits in every launch.  A row that is not 16-byte aligned (an odd ldl) loads the same groups by scalars: same sums.  No atomics.
+constexpr int kLpSlices = 32;
+constexpr int kLpMaxV = 262144;                   // kLpSlices slices x 256 threads x 8 groups x 4 columns
+
+template <int EPT>
+__global__ __launch_bounds__(256) void token_logp_slices_kernel(const float* logits, long ldl, int V, float* part) {
+    __shared__ float red[4];
+    const int row = (int)blockIdx.y, sl = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const int per = ((V + kLpSlices - 1) / kLpSlices + 3) & ~3;
+    const int lo = sl * per, hi = (lo + per) < V ? (lo + per) : V;          // (lo >= V: an empty slice -> (-3e38, 0))
+    const float* lr = logits + (long)row * ldl;
+    const bool vec = (reinterpret_cast<uintptr_t>(lr) & 15) == 0 && V >= 4;  // (uniform over the workgroup)
+    f32x4 v[EPT];
+    if (vec) {
+        // clamped, not branched around: a group that is not whole inside [lo, hi) re-reads group 0 of the row and is masked below
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+            const int c = lo + 4 * (tid + 256 * e);
+            v[e] = *reinterpret_cast<const f32x4*>(lr + (c + 4 <= hi ? c : 0));
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) v[e] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+        const int c = lo + 4 * (tid + 256 * e);
+        // every group of an unaligned row; of an aligned one only the ragged group at the row's end (hi = V, V % 4 != 0)
+        if (c < hi && (!vec || c + 4 > hi)) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[e][j] = lr[c + j < hi ? c + j : hi - 1];
+        }
+    }
+    float m = -3.0e38f;
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+        const int c = lo + 4 * (tid + 256 * e);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) m = c + j < hi ? fmaxf(m, v[e][j]) : m;
+    }
+    m = block_max<4>(m, red);
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+        const int c = lo + 4 * (tid + 256 * e);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s += c + j < hi ? __expf(v[e][j] - m) : 0.f;
+    }
+    s = block_sum<4>(s, red);
+    if (tid == 0) {
+        float* p = part + ((long)row * kLpSlices + sl) * 2;
+        p[0] = m;
+        p[1] = s;
+    }
+}
+
+// `T`: columns of tokens / out that exist — a step outside [0, T) writes nothing (the device word is not the host's to check)
+// (argument order: what the wave reads first lies in the 16 preloaded dwords; out / ldo, used last, are the ones past them)
+__global__ __launch_bounds__(64) void token_logp_merge_kernel(const float* part, const int* tokens, const int* step_ptr, int step_arg, int T,
+                                                              long ldt, const float* logits, long ldl, int V, float* out, long ldo) {
+    const int row = (int)blockIdx.x, lane = lane_id();
+    const int sl = lane < kLpSlices ? lane : 0;
+    const float pm = part[((long)row * kLpSlices + sl) * 2], ps = part[((long)row * kLpSlices + sl) * 2 + 1];
+    const int step = step_ptr ? step_ptr[0] : step_arg;
+    if (step < 0 || step >= T) return;            // (uniform over the wave)
+    const int tok = tokens[(long)row * ldt + step];
+    const bool ok = tok >= 0 && tok < V;
+    const float x = logits[(long)row * ldl + (ok ? tok : 0)];
+    const float mine_m = lane < kLpSlices ? pm : -3.0e38f;
+    const float M = wave_max<64>(mine_m);
+    const float S = wave_sum<64>(lane < kLpSlices ? ps * __expf(pm - M) : 0.f);
+    if (lane == 0) out[(long)row * ldo + step] = ok ? x - (M + __logf(S)) : 0.f;
+}
+
 // counters of the replayed token loop: pos[0 .. n) += 1 (rotary positions), a[0] += 1, b[0] += 1 (step index, cache length)
 // (one workgroup of up to 1024 threads: with 64 threads the n * hd row elements were 16 dependent position -> table round trips
 //  in series, 6.5 us per token for 4 KB)
@@ -1101,9 +1185,111 @@ __global__ __launch_bounds__(256) void grpo_loss_kernel(const float* logp, const
     }
 }
 
+// grpo_loss_kernel with truncated importance sampling against the rollout's own log-probs (bra_token_logp): every token's
+// policy-gradient term is weighted by w = min(exp(q - rollout_logp), is_cap), q = old_logp (or logp where there is none), w a
+// constant for the gradient; the KL term is not weighted.  out[0..3) as grpo_loss_kernel, out[3] = per-row masked mean of w averaged
+// over rows, out[4] = share of masked tokens with exp(q - rollout_logp) > is_cap, out[5] = per-row masked mean of rollout_logp - q
+// averaged over rows (KL(rollout || trainer) estimated on the sampled tokens).  The statements of grpo_loss_kernel in their order,
+// the two products by w kept as roundings of their own (pin_f32): with rollout_logp == q, w = exp(0) = 1 and out[0..3), dlogp are
+// that kernel's bits.
+#ifdef BRA_EMU
+__device__ __forceinline__ void pin_f32(float&) {}
+#else
+__device__ __forceinline__ void pin_f32(float& v) { asm volatile("" : "+v"(v)); }
+#endif
+
+__global__ __launch_bounds__(256) void grpo_loss_is_kernel(const float* logp, const float* old_logp, const float* ref_logp,
+                                                           const float* adv, const int* mask, const float* rollout_logp, int B, int C,
+                                                           float eps_lo, float eps_hi, float beta, float is_cap, float* out, float* dlogp) {
+    __shared__ float red[4];
+    const int tid = (int)threadIdx.x;
+    float loss_acc = 0.f, kl_acc = 0.f, clip_num = 0.f, mask_tot = 0.f, w_acc = 0.f, cap_num = 0.f, rkl_acc = 0.f;
+    for (int b = 0; b < B; ++b) {
+        float ms = 0.f;
+        for (int c = tid; c < C; c += 256) ms += (float)mask[(long)b * C + c];
+        ms = block_sum<4>(ms, red);
+        const float A = adv[b];
+        float ls = 0.f, ks = 0.f, cs = 0.f, ws = 0.f, ns = 0.f, rs = 0.f;
+        for (int c = tid; c < C; c += 256) {
+            const long i = (long)b * C + c;
+            const float lp = logp[i];
+            const float ol = old_logp ? old_logp[i] : lp;
+            const float mk = (float)mask[i];
+            const float rl = rollout_logp[i];
+            const float we = __expf(ol - rl);
+            const float w = fminf(we, is_cap);
+            const float c1 = __expf(lp - ol);
+            const float c2 = fminf(fmaxf(c1, 1.f - eps_lo), 1.f + eps_hi);
+            const float l1 = c1 * A, l2 = c2 * A;
+            float ptl = w * -fminf(l1, l2);
+            pin_f32(ptl);
+            const float g1 = -A * c1;
+            const float g2 = (c1 >= 1.f - eps_lo && c1 <= 1.f + eps_hi) ? -A * c1 : 0.f;
+            float g = w * (l1 < l2 ? g1 : (l1 > l2 ? g2 : 0.5f * (g1 + g2)));
+            pin_f32(g);
+            if (beta != 0.f && ref_logp) {
+                const float dl = ref_logp[i] - lp;
+                const float e = __expf(dl);
+                const float kl = e - dl - 1.f;
+                ptl += beta * kl;
+                g += beta * (1.f - e);
+                ks += kl * mk;
+            }
+            ls += ptl * mk;
+            cs += (l1 < l2 ? 1.f : 0.f) * mk;
+            ws += w * mk;
+            ns += (we > is_cap ? 1.f : 0.f) * mk;
+            rs += (rl - ol) * mk;
+            if (dlogp) dlogp[i] = ms > 0.f ? g * mk / (ms * (float)B) : 0.f;
+        }
+        ls = block_sum<4>(ls, red);
+        ks = block_sum<4>(ks, red);
+        cs = block_sum<4>(cs, red);
+        ws = block_sum<4>(ws, red);
+        ns = block_sum<4>(ns, red);
+        rs = block_sum<4>(rs, red);
+        loss_acc += ls / ms;
+        kl_acc += ks / ms;
+        clip_num += cs;
+        mask_tot += ms;
+        w_acc += ws / ms;
+        cap_num += ns;
+        rkl_acc += rs / ms;
+    }
+    if (tid == 0) {
+        out[0] = loss_acc / (float)B;
+        out[1] = kl_acc / (float)B;
+        out[2] = clip_num / mask_tot;
+        out[3] = w_acc / (float)B;
+        out[4] = cap_num / mask_tot;
+        out[5] = rkl_acc / (float)B;
+    }
+}
+
 }  // namespace bra
 
 using namespace bra;
+
+// out[b * ldo + t] = logits[b, tokens[b * ldt + t]] - logsumexp(logits[b, 0 .. V)), t = *step_ptr or `step` (step_ptr null) — see
+// token_logp_slices_kernel.  ws: bra_token_logp_ws_floats(B) floats.  T: the columns tokens / out have; a device step outside
+// [0, T) writes nothing.  A recorded id outside [0, V) gives 0.0.
+extern "C" int bra_token_logp_ws_floats(int B) { return 2 * kLpSlices * (B > 0 ? B : 0); }
+
+extern "C" int bra_token_logp(const float* logits, long ldl, int B, int V, const int* tokens, long ldt, int T, const int* step_ptr,
+                              int step, float* out, long ldo, float* ws, void* stream) {
+    if (!logits || !tokens || !out || !ws || B < 1 || V < 1 || ldl < V || T < 1 || ldt < T || ldo < T) return BRA_ERR_ARG;
+    if (!step_ptr && (step < 0 || step >= T)) return BRA_ERR_ARG;
+    if (B > 64 || V > kLpMaxV) return BRA_ERR_UNSUPPORTED;
+    const int per = ((V + kLpSlices - 1) / kLpSlices + 3) & ~3;
+    if (per <= 1024) BRA_LAUNCH(token_logp_slices_kernel<1>, dim3(kLpSlices, B), dim3(256), 0, stream, logits, ldl, V, ws);
+    else if (per <= 5120) BRA_LAUNCH(token_logp_slices_kernel<5>, dim3(kLpSlices, B), dim3(256), 0, stream, logits, ldl, V, ws);
+    else BRA_LAUNCH(token_logp_slices_kernel<8>, dim3(kLpSlices, B), dim3(256), 0, stream, logits, ldl, V, ws);
+    int r = BRA_LAUNCH_STATUS();
+    if (r) return r;
+    BRA_LAUNCH(token_logp_merge_kernel, dim3(B), dim3(64), 0, stream, (const float*)ws, tokens, step_ptr, step, T, ldt, logits, ldl, V,
+               out, ldo);
+    return BRA_LAUNCH_STATUS();
+}
 
 extern "C" int bra_sample_ws_floats(int B, int top_k) {     // workspace size in 4-byte words (values + indices)
     const int k = top_k > 0 ? (top_k < 64 ? top_k : 64) : 64;
@@ -1350,5 +1536,16 @@ extern "C" int bra_grpo_loss(const float* logp, const float* old_logp, const flo
     if (B <= 0 || C <= 0 || !logp || !adv || !mask || !out3) return BRA_ERR_ARG;
     BRA_LAUNCH(grpo_loss_kernel, dim3(1), dim3(256), 0, stream, logp, old_logp, ref_logp, adv, mask, B, C, eps_lo,
                eps_hi, beta, out3, dlogp);
+    return BRA_LAUNCH_STATUS();
+}
+
+// bra_grpo_loss with truncated importance sampling (see grpo_loss_is_kernel): rollout_logp [B, C] = what bra_token_logp recorded,
+// is_cap >= 1, out6 = {loss, mean_kl, clip_ratio, is_mean, is_capped, rollout_kl}
+extern "C" int bra_grpo_loss_is(const float* logp, const float* old_logp, const float* ref_logp, const float* adv, const int* mask,
+                                const float* rollout_logp, int B, int C, float eps_lo, float eps_hi, float beta, float is_cap,
+                                float* out6, float* dlogp, void* stream) {
+    if (B <= 0 || C <= 0 || !logp || !adv || !mask || !out6 || !rollout_logp || !(is_cap >= 1.f)) return BRA_ERR_ARG;
+    BRA_LAUNCH(grpo_loss_is_kernel, dim3(1), dim3(256), 0, stream, logp, old_logp, ref_logp, adv, mask, rollout_logp, B, C, eps_lo,
+               eps_hi, beta, is_cap, out6, dlogp);
     return BRA_LAUNCH_STATUS();
 }

@@ -743,13 +743,25 @@ def _generate_in_row_chunks(model, inputs_embeds, attention_mask, prompt_alias, 
     if trace is not None:                                                          # per step: the chunks' logits stacked back into [B, V]
         for t_ in range(max(len(tr) for tr in traces)):
             trace.append(torch.cat([tr[min(t_, len(tr) - 1)] for tr in traces], 0))
+    lps = None
+    if kw.get("return_logprobs"):                                                  # every chunk returned (tokens, logprobs)
+        outs, lps = [o[0] for o in outs], [o[1] for o in outs]
     T = max(o.shape[1] for o in outs)
     full = torch.full((B, T), pad, dtype=torch.long, device=inputs_embeds.device)
     r = 0
     for o in outs:
         full[r:r + o.shape[0], :o.shape[1]] = o
         r += o.shape[0]
-    return full
+    if lps is None:
+        return full
+    # the chunks' log-prob matrices stitched back like the tokens; a chunk that stopped earlier than the widest one is all-finished
+    # from there on: 0.0, as after any EOS
+    full_lp = torch.zeros((B, T), dtype=torch.float32, device=inputs_embeds.device)
+    r = 0
+    for o in lps:
+        full_lp[r:r + o.shape[0], :o.shape[1]] = o
+        r += o.shape[0]
+    return full, full_lp
 
 
 @torch.no_grad()
@@ -763,7 +775,7 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
              eos_schedule: Optional[torch.Tensor] = None, trace_logits: Optional[list] = None,
              repetition_penalty: float = 1.0, min_new_tokens: int = 0, min_p: Optional[float] = None,
              no_repeat_ngram_size: int = 0, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None,
-             sequence_bias=None) -> torch.Tensor:
+             sequence_bias=None, return_logprobs: bool = False):
     """`force_tokens` [B, max_new_tokens] (optional): teacher forcing — the model's own choice is still recorded
     in the output, but the given token is fed back (used to compare decodes position by position).
     `use_graph`: True = sample + decode step + counter update are captured once in a hipGraph and replayed per token
@@ -784,7 +796,16 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
     same names, validated as HF validates them, over the generated tokens only (begin_index 0) and in HF's order: sequence bias ->
     penalty -> n-gram -> bad words -> min length -> suppress -> begin suppress.  One addition: a bias must be finite or -inf.  With one
     of them on, ops.logits_process_ext runs the whole chain in one launch INSTEAD of ops.logits_process; its fixed limits
-    (ops.ProcessorTables) are a ValueError here, before any launch."""
+    (ops.ProcessorTables) are a ValueError here, before any launch.
+    `return_logprobs`: True -> (tokens, logprobs): fp32 [B, T], shaped and trimmed like `tokens`; logprobs[b, t] is the log-probability
+    the ROLLOUT's own network gave the recorded token: log-softmax of the step's raw fp32 logits over the whole vocabulary at
+    temperature 1 (ops.token_logp, issued after every draw and before the decode step overwrites the logits) — the quantity
+    `_get_per_token_logps` computes on the training side, independent of temperature / top-k / top-p / min-p, which only shape the
+    draw.  Under `force_tokens` it belongs to the recorded token (the model's own choice), under `eos_schedule` it is taken over the
+    logits as the schedule left them (the scheduled EOS has log-probability 0.0), and every position after a row's first EOS holds
+    exactly 0.0.  The logits processors (`repetition_penalty` != 1, `min_new_tokens` > 0, n-gram / bad words / suppress / sequence bias)
+    edit the logits in place in front of the sampler, so the raw value of the drawn token is gone after the draw: together with
+    `return_logprobs=True` they are a ValueError, before any launch.  Off (default): the loop issues what it issued before."""
     _call_kw = dict(locals())                      # every argument of this call, by name (forwarded whole by the row-chunk path)
     # validation as HF's processors (TF:generation/logits_process.py), plus the bound of the kernel's history staging
     if isinstance(repetition_penalty, bool) or not isinstance(repetition_penalty, (int, float)) or not repetition_penalty > 0:
@@ -800,6 +821,13 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
     min_p_dev = float(min_p) if (do_sample and min_p is not None) else 0.0
     ctl = _validated_controls(no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens, sequence_bias,
                               _eos_ids(eos_token_id, pad_token_id)[:2])
+    if return_logprobs and (process or ctl is not None):
+        on = [n for n, v in (("repetition_penalty", repetition_penalty != 1.0), ("min_new_tokens", min_new_tokens > 0),
+                             ("no_repeat_ngram_size", bool(ctl and ctl["ngram"])), ("bad_words_ids", bool(ctl and ctl["bad_words"])),
+                             ("suppress_tokens", bool(ctl and ctl["suppress"])), ("begin_suppress_tokens", bool(ctl and ctl["begin_suppress"])),
+                             ("sequence_bias", bool(ctl and ctl["sequence_bias"]))) if v]
+        raise ValueError(f"`return_logprobs=True` cannot be combined with the logits processors ({', '.join(on)}): they edit the logits in "
+                         "place in front of the sampler, so the rollout's raw log-probability of the drawn token is gone after the draw")
     eng = model.ensure_packed()
     B, P, H = inputs_embeds.shape
     dev = inputs_embeds.device
@@ -866,6 +894,9 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
     cur = torch.empty((B,), dtype=torch.int32, device=dev)
     step_t = torch.zeros((1,), dtype=torch.int32, device=dev)
     logits = torch.empty((B, eng.V), dtype=torch.float32, device=dev)
+    # return_logprobs: one fp32 per recorded token (zeros where no draw happens) + the slice partials of ops.token_logp, 64 rows a launch
+    logps = torch.zeros((B, max_new_tokens), dtype=torch.float32, device=dev) if return_logprobs else None
+    lp_ws = ops.token_logp_ws(min(B, 64), dev) if return_logprobs else None
     n_done = max_new_tokens
     kk = (min(top_k, 64) if top_k > 0 else 64) if do_sample else 1
     sample_ws = torch.empty((2 * B * 64 * kk,), dtype=torch.float32, device=dev) if eng.V >= 4096 else None
@@ -920,6 +951,12 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
         elif process:
             ops.logits_process(logits, hist, st, repetition_penalty, min_new_tokens, eos, eos2, fin_, tm)
 
+    def logp_(st):
+        """return_logprobs: the recorded token's log-probability under the logits the draw just read (nothing when the flag is off)"""
+        if logps is not None:
+            for r0 in range(0, B, 64):
+                ops.token_logp(logits[r0:r0 + 64], tokens[r0:r0 + 64], st, logps[r0:r0 + 64], lp_ws)
+
     def sample_(t_host: Optional[int] = None):
         """the draw of step t.  `t_host` given: launch-by-launch issue (the index travels as an argument where the kernels take it)"""
         host_step = t_host is not None and fuse_adv
@@ -934,12 +971,14 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
                              eos_id2=eos2, tokens_out=tokens, ws=sample_ws, embed=emb,
                              advance=(pos0, next_pos, rope_args[0], rope_args[1], rope_args[2], rope_args[3]) if host_step else None,
                              min_p=min_p_dev)
+            logp_(st)
             return
         if eos_schedule is not None:
             ops.force_token(logits, eos, step_t, eos_schedule)
         process_(step_t, None)
         ops.sample(logits, temperature, top_k, top_p, do_sample, seed, step_t, fin, pad,
                    cur, None, eos_id=eos, eos_id2=eos2, tokens_out=tokens, ws=sample_ws, embed=emb, min_p=min_p_dev)
+        logp_(step_t)
 
     def advance_(t_grid: int, exact_t: bool = False):
         """one fused decode step.  Under graph replay the kernels take the step index from step_t / len_t and `t_grid` only sizes
@@ -1072,10 +1111,20 @@ def generate(model, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, m
         del graph
         _tick("graph_reset")
     out = tokens[:, :n_done]
+    lp = None
+    if logps is not None:
+        lp = logps[:, :n_done]
+        if eos >= 0:
+            # one masked fill per call: a finished row records pad, whose value under the logits is not a draw's — exactly 0.0 there
+            e_ = ((out == eos) | (out == eos2) if eos2 >= 0 else out == eos).to(torch.int32)
+            lp.masked_fill_((e_.cumsum(dim=1) - e_) > 0, 0.0)
     if eos >= 0 and not return_full_length and force_tokens is None:
         # HF stops right after the step in which the last row finished: trim the all-pad tail we may have produced
         is_eos = (out == eos) | (out == eos2) if eos2 >= 0 else out == eos
         has = is_eos.any(dim=1)
         first = torch.where(has, is_eos.int().argmax(dim=1), torch.full_like(has, out.shape[1] - 1, dtype=torch.long))
         out = out[:, : int(first.max().item()) + 1]
+        lp = lp[:, : out.shape[1]] if lp is not None else None
+    if lp is not None:
+        return out.to(torch.long), lp.contiguous()
     return out.to(torch.long)

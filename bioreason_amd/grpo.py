@@ -57,10 +57,33 @@ class _GrpoLossFn(torch.autograd.Function):
         return dlogp * g, None, None, None, None, None, None, None
 
 
-def grpo_loss(logp, old_logp, ref_logp, advantages, mask, epsilon_low=0.2, epsilon_high=0.2, beta=0.04):
-    """-> (loss, stats[3] = {loss, mean_kl, clip_ratio}); old_logp=None <=> num_iterations == 1 (:786)."""
+class _GrpoLossIsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logp, old_logp, ref_logp, adv, mask, rollout_logp, eps_lo, eps_hi, beta, is_cap):
+        out6, dlogp = ops.grpo_loss_is(logp.contiguous(), old_logp, ref_logp, adv.contiguous().float(), mask.contiguous(), rollout_logp,
+                                       eps_lo, eps_hi, beta, is_cap, need_grad=True)
+        ctx.save_for_backward(dlogp)
+        ctx.mark_non_differentiable(out6)
+        return out6[0].clone(), out6
+
+    @staticmethod
+    def backward(ctx, g, _g6):
+        (dlogp,) = ctx.saved_tensors
+        return dlogp * g, None, None, None, None, None, None, None, None, None
+
+
+def grpo_loss(logp, old_logp, ref_logp, advantages, mask, epsilon_low=0.2, epsilon_high=0.2, beta=0.04, rollout_logp=None, is_cap=2.0):
+    """-> (loss, stats[3] = {loss, mean_kl, clip_ratio}); old_logp=None <=> num_iterations == 1 (:786).
+    `rollout_logp` fp32 [B, C] (generate(return_logprobs=True)): truncated importance sampling against the rollout's own policy — every
+    token's policy-gradient term is weighted by min(pi_trainer / pi_rollout, is_cap), the weight a constant for the gradient
+    (bra_grpo_loss_is) -> (loss, stats[6] = {loss, mean_kl, clip_ratio, is_mean, is_capped, rollout_kl}).  None: the loss above."""
     rl = ref_logp.contiguous() if (ref_logp is not None and beta != 0.0) else None
     ol = old_logp.contiguous() if old_logp is not None else None
+    if rollout_logp is not None:
+        if not is_cap >= 1.0:
+            raise ValueError(f"`is_cap` has to be >= 1 (a cap below 1 would down-weight on-policy tokens), but is {is_cap!r}")
+        return _GrpoLossIsFn.apply(logp, ol, rl, advantages, mask.to(torch.int32), rollout_logp.detach().float().contiguous(),
+                                   epsilon_low, epsilon_high, beta, float(is_cap))
     return _GrpoLossFn.apply(logp, ol, rl, advantages, mask.to(torch.int32), epsilon_low, epsilon_high, beta)
 
 

@@ -165,6 +165,11 @@ class DNALLMGRPOConfig(TrainingArguments):
     # ---- not in the reference: stream fp8 (e4m3, one scale per output row) images of the merged weights in the rollout's token loop
     # (BASELINE config 5; bioreason_amd.trainer.GRPOConfig.rollout_fp8)
     rollout_fp8: bool = field(default=False)
+    # ---- not in the reference: truncated importance sampling against the rollout's own policy (bioreason_amd.trainer.GRPOConfig.
+    # rollout_is_correction / rollout_is_cap): the token loop reports the log-probability it drew every token under, the loss weights the
+    # policy-gradient term by min(pi_trainer / pi_rollout, cap), and is_mean / is_capped / rollout_kl are logged beside kl and clip_ratio
+    rollout_is_correction: bool = field(default=False)
+    rollout_is_cap: float = field(default=2.0)
     # ---- not in the reference: > 1 = `LengthBucketedRepeatSampler` — the global batches of a window of this many batches hold prompts of
     # similar expected cost (prompt + DNA length, refined by observed completion lengths), so the ranks of a step finish closer together
     # at the gather barrier; 1 (default) = the reference's RepeatRandomSampler, index for index
@@ -252,7 +257,9 @@ class DNALLMGRPOTrainer:
                          adam_beta2=args.adam_beta2, adam_epsilon=args.adam_epsilon, max_grad_norm=args.max_grad_norm,
                          eos_token_id=self.processing_class.eos_token_id, pad_token_id=pad_token_id,
                          seed=args.seed, share_policy_prompt=getattr(args, "share_policy_prompt", None),
-                         rollout_fp8=bool(getattr(args, "rollout_fp8", False)))
+                         rollout_fp8=bool(getattr(args, "rollout_fp8", False)),
+                         rollout_is_correction=bool(getattr(args, "rollout_is_correction", False)),
+                         rollout_is_cap=float(getattr(args, "rollout_is_cap", 2.0)))
         self.runner = GRPOStepRunner(model, cfg)
         self.state = SimpleNamespace(global_step=0, epoch=0.0, log_history=self.log_history)
         model.train()                                               # HF Trainer.training_step puts the model in train mode

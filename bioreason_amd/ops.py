@@ -618,6 +618,28 @@ def logits_process(logits: torch.Tensor, hist: Optional[torch.Tensor], step, pen
     return logits
 
 
+def token_logp_ws(B: int, device) -> torch.Tensor:
+    """workspace of `token_logp` for B rows (the slice partials: bra_token_logp_ws_floats)"""
+    return torch.empty((int(get_lib()._dll.bra_token_logp_ws_floats(int(B))),), dtype=torch.float32, device=device)
+
+
+def token_logp(logits: torch.Tensor, tokens: torch.Tensor, step, out: torch.Tensor, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[b, t] = logits[b, tokens[b, t]] - logsumexp(logits[b, :]): the log-probability of the token recorded at step t under the raw
+    fp32 logits [B, V] of that step (temperature 1, whole vocabulary, independent of the warpers).  `tokens` int32 [B, T] and `out`
+    fp32 [B, T] (any row pitch); `step` = t: device int32 [1] (replayed loops) or python int.  `ws`: token_logp_ws(B, device)."""
+    B, V = logits.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and tokens.dtype == torch.int32 and tokens.stride(1) == 1
+    assert out.dtype == torch.float32 and out.stride(1) == 1 and tokens.shape[0] == B and out.shape[0] == B
+    if ws is None:
+        ws = token_logp_ws(B, logits.device)
+    step_ptr, step_i = (step, 0) if isinstance(step, torch.Tensor) else (None, int(step))
+    T = min(tokens.shape[1], out.shape[1])
+    # (a one-row tensor may carry any stride(0): the pitch of a single row is its width)
+    ldl, ldt, ldo = (_ld(logits), tokens.stride(0), out.stride(0)) if B > 1 else (max(_ld(logits), V), max(tokens.stride(0), T), max(out.stride(0), T))
+    get_lib().call("bra_token_logp", logits, ldl, B, V, tokens, ldt, T, step_ptr, step_i, out, ldo, ws, current_stream(logits))
+    return out
+
+
 class ProcessorTables:
     """Device tables of `logits_process_ext`, built once per generate() call.
     `sequence_bias`: {tuple of ids: bias} (bias finite or -inf); `bad_words`: list of lists of ids (the caller has dropped [eos]);
@@ -885,6 +907,18 @@ def grpo_loss(logp, old_logp, ref_logp, adv, mask, eps_lo, eps_hi, beta, need_gr
     dlogp = torch.empty_like(logp) if need_grad else None
     get_lib().call("bra_grpo_loss", logp, old_logp, ref_logp, adv, mask, B, C, eps_lo, eps_hi, beta, out3, dlogp, current_stream(logp))
     return out3, dlogp
+
+
+def grpo_loss_is(logp, old_logp, ref_logp, adv, mask, rollout_logp, eps_lo, eps_hi, beta, is_cap, need_grad=True):
+    """grpo_loss with truncated importance sampling against the rollout's log-probs (bra_grpo_loss_is) ->
+    (out6 = [loss, mean_kl, clip_ratio, is_mean, is_capped, rollout_kl], dlogp)"""
+    B, C = logp.shape
+    assert rollout_logp is None or (rollout_logp.dtype == torch.float32 and rollout_logp.shape == logp.shape and rollout_logp.is_contiguous())
+    out6 = torch.empty((6,), dtype=torch.float32, device=logp.device)
+    dlogp = torch.empty_like(logp) if need_grad else None
+    get_lib().call("bra_grpo_loss_is", logp, old_logp, ref_logp, adv, mask, rollout_logp, B, C, eps_lo, eps_hi, beta, float(is_cap), out6,
+                   dlogp, current_stream(logp))
+    return out6, dlogp
 
 
 def cast_grad(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:

@@ -78,6 +78,14 @@ class GRPOConfig:
     # prompt pass); ref_fp8 also runs the no-grad REFERENCE pass that way over e4m3 images of the base weights (the KL term then measures
     # the distance to the quantised reference policy).  The policy pass and every gradient stay bf16.
     ref_fp8: bool = False
+    # opt-in: truncated importance sampling against the ROLLOUT's own policy.  The token loop records, per drawn token, the log-probability
+    # its own network gave it (generate(return_logprobs=True): raw logits, temperature 1, whole vocabulary — the quantity the policy pass
+    # computes); the loss weights every token's policy-gradient term by min(pi_trainer / pi_rollout, rollout_is_cap) (grpo.grpo_loss) and
+    # the step reports is_mean, is_capped and rollout_kl.  What it corrects: the merged / norm-folded bf16 rollout weights and, with
+    # rollout_fp8, their quantisation — not the temperature / top-k / top-p warpers (the reference is off-policy there by design).  Not
+    # together with the rollout's logits processors (the raw value of a drawn token is gone once they have edited the logits).
+    rollout_is_correction: bool = False
+    rollout_is_cap: float = 2.0
     grad_buckets: int = 4
     # transport dtype of the gradient all-reduce: "fp32" (default: the flat arena itself, 148 MB) or "bf16" (each bucket is rounded to a
     # bf16 image, summed over the ranks in bf16 and widened back: half the xGMI bytes, one rounding per rank and per sum step — DDP's
@@ -282,6 +290,17 @@ class GRPOStepRunner(_DataParallelStep):
     def __init__(self, model, cfg: GRPOConfig, reward_fn: Callable = token_stat_rewards):
         super().__init__(model, cfg.grad_buckets, getattr(cfg, "grad_allreduce_dtype", "fp32"))
         self.cfg, self.reward_fn = cfg, reward_fn
+        self.is_correction = bool(getattr(cfg, "rollout_is_correction", False))
+        if self.is_correction:
+            cap = getattr(cfg, "rollout_is_cap", 2.0)
+            if not cap >= 1.0:
+                raise ValueError(f"`rollout_is_cap` has to be >= 1, but is {cap!r}")
+            clash = [n for n, v in (("repetition_penalty", cfg.repetition_penalty != 1.0), ("no_repeat_ngram_size", bool(cfg.no_repeat_ngram_size)),
+                                    ("bad_words_ids", bool(cfg.bad_words_ids)), ("suppress_tokens", bool(cfg.suppress_tokens))) if v]
+            if clash:
+                raise ValueError(f"`rollout_is_correction=True` cannot be combined with the rollout's logits processors ({', '.join(clash)}): "
+                                 "the token loop cannot report the raw log-probability of a token drawn from processed logits")
+            self.metric_names = list(self.metric_names) + ["is_mean", "is_capped", "rollout_kl"]
         self.global_step = 0                # optimiser steps (HF: self.state.global_step)
         self._step = 0                      # forward/backward passes, incl. those inside an accumulation cycle (:395)
         self.step_idx = 0                   # rollouts generated (seeds the sampler)
@@ -351,6 +370,7 @@ class GRPOStepRunner(_DataParallelStep):
             torch.cuda.current_stream(dev).wait_stream(wside)
         sched = batch.get("eos_schedule")
         # rollout (unwrapped_model.generate, :579-596): only completion ids come back
+        gen_kw = {"return_logprobs": True} if self.is_correction else {}      # (off: the call of before, keyword for keyword)
         completion_ids = m.generate(input_ids=prompt_ids, attention_mask=prompt_mask, **mm,
                                     max_new_tokens=c.max_completion_length, do_sample=True, temperature=c.temperature,
                                     top_k=c.top_k, top_p=c.top_p, repetition_penalty=c.repetition_penalty, min_p=c.min_p,
@@ -360,7 +380,10 @@ class GRPOStepRunner(_DataParallelStep):
                                     seed=c.seed + 1000003 * self.step_idx + self.rank, return_full_length=sched is None,
                                     prompt_alias=batch.get("prompt_alias"), use_graph=c.rollout_graph,
                                     shared_prefix_decode=c.rollout_shared_prefix, eos_schedule=sched,
-                                    profile=self.rollout_profile if timing else None, loop_events=self.loop_events)
+                                    profile=self.rollout_profile if timing else None, loop_events=self.loop_events, **gen_kw)
+        rollout_lp = None
+        if self.is_correction:
+            completion_ids, rollout_lp = completion_ids
         self.step_idx += 1
         mark("rollout")
         if c.eos_token_id is not None:
@@ -420,7 +443,7 @@ class GRPOStepRunner(_DataParallelStep):
             ref_join = None
         return {"prompt_ids": prompt_ids, "prompt_mask": prompt_mask, "completion_ids": completion_ids, "completion_mask": cmask,
                 "old_per_token_logps": old_lp, "ref_per_token_logps": ref_lp, "advantages": adv, "multimodal_inputs": mm,
-                "prompt_alias": batch.get("prompt_alias"), "ref_join": ref_join,
+                "prompt_alias": batch.get("prompt_alias"), "ref_join": ref_join, "rollout_per_token_logps": rollout_lp,
                 "rewards_per_func": all_rewards.mean(0), "roll_metrics": roll_metrics}
 
     def shares_policy_prompt(self) -> bool:
@@ -447,6 +470,9 @@ class GRPOStepRunner(_DataParallelStep):
         if inputs.get("ref_join") is not None:                       # the reference pass ran beside the policy forward: join
             torch.cuda.current_stream(lp.device).wait_stream(inputs["ref_join"])
             inputs["ref_join"] = None
+        if self.is_correction:
+            return grpo.grpo_loss(lp, old, inputs["ref_per_token_logps"], inputs["advantages"], inputs["completion_mask"],
+                                  c.epsilon, eps_hi, c.beta, rollout_logp=inputs["rollout_per_token_logps"], is_cap=c.rollout_is_cap)
         return grpo.grpo_loss(lp, old, inputs["ref_per_token_logps"], inputs["advantages"], inputs["completion_mask"],
                               c.epsilon, eps_hi, c.beta)
 
@@ -475,14 +501,14 @@ class GRPOStepRunner(_DataParallelStep):
         loss, stats = self.compute_loss(inputs)
         mark("policy_fwd")
         if self.dp:                         # loss / KL / clip ratio of this rank ride in the gradient bucket's spare slot
-            m.arena.grad(METRIC_SLOT).view(-1)[:3].add_(stats / ga)
+            m.arena.grad(METRIC_SLOT).view(-1)[:stats.numel()].add_(stats / ga)
         (loss / ga if ga > 1 else loss).backward()
         mark("policy_bwd")
         out = {"loss_t": loss.detach(), "stats_t": stats, "reward_mean_t": inputs["roll_metrics"][1]}
         if slot == ga - 1:
             scale = self.reduce_gradients()
             if self.dp:
-                local3 = m.arena.grad(METRIC_SLOT).view(-1)[:3] * scale
+                local3 = m.arena.grad(METRIC_SLOT).view(-1)[:stats.numel()] * scale
             else:
                 local3 = stats
             lr = c.learning_rate if self.lr_schedule is None else float(self.lr_schedule(self.global_step))

@@ -443,6 +443,19 @@ int bra_sample_tiles(const float* logits, long ldl, const float* tmax, long ldm,
 int bra_sample_full(const float* logits, long ldl, int B, int V, float temperature, int top_k, float top_p, unsigned seed,
                     const int* step_ptr, int step, void* finished, int pad_id, int eos_id, int eos_id2, int* out_ids,
                     float* out_logp, int* tokens_out, long ldt, float min_p, void* stream);
+/* Log-probability of the token a draw RECORDED, under the step's own logits: out[b * ldo + t] = logits[b, tok] - logsumexp_v(logits[b,
+ * 0 .. V)) with tok = tokens[b * ldt + t] and t = *step_ptr (device int: replayed loops) or `step` when step_ptr is null, as for
+ * bra_sample_tiles.  Raw logits, temperature 1, the whole vocabulary: independent of the warpers, and the quantity the training side
+ * computes for the same token (_get_per_token_logps, grpo_trainer.py:492-506).  Issued after the draw of step t and before the
+ * decode step overwrites `logits`.  Two launches: 32 vocabulary slices per row (16-byte loads, slice maximum and sum of
+ * exponentials over registers), then one wave per row merges the slices in a fixed order; no atomics.  The slice partition and the
+ * merge order depend on V alone: row b's value is bit-identical whatever B is, whichever rows share the launch, and wherever the
+ * step index came from.  T: the columns `tokens` and `out` have (ldt, ldo >= T); a device step outside [0, T) writes nothing; a
+ * recorded id outside [0, V) gives 0.0.  ws: bra_token_logp_ws_floats(B) floats.  1 <= B <= 64, 1 <= V <= 262144, ldl >= V (any
+ * V, any alignment of the rows); BRA_ERR_UNSUPPORTED beyond those sizes, BRA_ERR_ARG otherwise, nothing written on refusal. */
+int bra_token_logp(const float* logits, long ldl, int B, int V, const int* tokens, long ldt, int T, const int* step_ptr, int step,
+                   float* out, long ldo, float* ws, void* stream);
+int bra_token_logp_ws_floats(int B);
 /* bra_force_token that also raises the token's tile maximum; `step_ptr` null: the step index is `step` */
 int bra_force_token_tiles(float* logits, long ldl, int B, int V, int token, const int* step_ptr, int step, const int* at,
                           float* tmax, long ldm, void* stream);
@@ -500,6 +513,16 @@ int bra_group_advantage(const float* rewards, int N, int F, int G, float* adv, f
 /* compute_loss (grpo_trainer.py:786-814): out3 = {loss, mean_kl, clip_ratio}; dlogp = dloss/dlogp */
 int bra_grpo_loss(const float* logp, const float* old_logp, const float* ref_logp, const float* adv, const int* mask,
                   int B, int C, float eps_lo, float eps_hi, float beta, float* out3, float* dlogp, void* stream);
+/* bra_grpo_loss with truncated importance sampling against the ROLLOUT's log-probs (rollout_logp [B, C], what bra_token_logp
+ * recorded while the tokens were drawn): with q = old_logp (logp where old_logp is null), w = min(exp(q - rollout_logp), is_cap) — a
+ * constant for the gradient — the per-token loss is w (-min(l1, l2)) + beta kl and dlogp = (w g_pg + beta (1 - e)) mask / (ms B), g_pg
+ * the policy-gradient part of bra_grpo_loss.  out6 = {loss, mean_kl, clip_ratio, is_mean, is_capped, rollout_kl}: is_mean the per-row
+ * masked mean of w averaged over rows, is_capped the share of masked tokens with exp(q - rollout_logp) > is_cap, rollout_kl the
+ * per-row masked mean of rollout_logp - q averaged over rows (KL(rollout || trainer) on the sampled tokens).  Where rollout_logp
+ * equals q bit for bit, out6[0..3) and dlogp are bra_grpo_loss's bits.  is_cap < 1 or a null rollout_logp: BRA_ERR_ARG. */
+int bra_grpo_loss_is(const float* logp, const float* old_logp, const float* ref_logp, const float* adv, const int* mask,
+                     const float* rollout_logp, int B, int C, float eps_lo, float eps_hi, float beta, float is_cap, float* out6,
+                     float* dlogp, void* stream);
 
 /* out[r, 0..n) = (add ? add[r] : 0) + sum over the `copies` members c of group r of src[(r copies + c) member_stride + 0..n), bf16
  * in / out, fp32 accumulation: the gradient the G rollouts of a GRPO group (grpo_trainer.py:107-116) send to the rows they share
