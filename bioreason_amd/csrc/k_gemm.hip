@@ -29,6 +29,8 @@ enum : int {
     EPI_DLOGIT = 3,   // C bf16 = rnd(coef[m] * ((n==tgt[m]) - exp(rnd(acc) - lse[m])))
     EPI_ATOMIC = 4,   // C f32 += alpha*acc with atomics (split-K)
     EPI_SWIGLU = 5,   // ring kernel only: B = [gate rows | up rows] ([2 F, K]); C bf16 [M, F] = rnd(rnd(silu(rnd(g))) * rnd(u)) (no-grad passes)
+    EPI_LSE_ENT = 6,  // EPI_LSE + part_xs[m, chunk] = sum_j exp(x_j - vmax) (x_j - vmax): the chunk's share of the row's entropy
+    EPI_DLOGIT_ENT = 7,  // C bf16 = rnd(coef[m] ((n==tgt[m]) - p) - ecoef[m] p (x - lse[m] + ent[m])), p = exp(x - lse[m]), x = rnd(acc)
 };
 
 struct GemmArgs {
@@ -51,6 +53,10 @@ struct GemmArgs {
     float* tgt_logit;     // [M]
     const float* lse;     // [M]
     const float* coef;    // [M]
+    // EPI_LSE_ENT / EPI_DLOGIT_ENT
+    float* part_xs;       // [M, nchunk]
+    const float* ent;     // [M] row entropy (bra_lse_ent_merge)
+    const float* ecoef;   // [M] dL/d ent
     int nchunk;
     int swiglu_F;         // EPI_SWIGLU: F (N = 2 F); B row of local tile row `loc` = (loc >> 5) * 16 + (loc & 15) + 128 tile_n (+ F when loc & 16)
 };
@@ -253,13 +259,15 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4 (&acc)[4]
     }
     const int fr = lane & 15, fq = lane >> 4;
     const float alpha = g.alpha;
-    if (EPI == EPI_BF16 || EPI == EPI_F32 || EPI == EPI_ATOMIC || EPI == EPI_DLOGIT) {
+    if (EPI == EPI_BF16 || EPI == EPI_F32 || EPI == EPI_ATOMIC || EPI == EPI_DLOGIT || EPI == EPI_DLOGIT_ENT) {
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {
             const int m = m0 + wm * 64 + mi * 16 + fr;
             if (m >= g.M) continue;
             float lse_m = 0.f, coef_m = 0.f; int tgt_m = -1;
-            if (EPI == EPI_DLOGIT) { lse_m = g.lse[m]; coef_m = g.coef[m]; tgt_m = g.tgt[m]; }
+            float ent_m = 0.f, ecoef_m = 0.f;
+            if (EPI == EPI_DLOGIT || EPI == EPI_DLOGIT_ENT) { lse_m = g.lse[m]; coef_m = g.coef[m]; tgt_m = g.tgt[m]; }
+            if (EPI == EPI_DLOGIT_ENT) { ent_m = g.ent[m]; ecoef_m = g.ecoef[m]; }
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) {
                 const int n = n0 + wn * 64 + ni * 16 + fq * 4;
@@ -298,6 +306,21 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4 (&acc)[4]
                     } else {
                         for (int r = 0; r < 4; ++r) if (n + r < g.N) cp[r] = f2bf(v[r]);
                     }
+                } else if (EPI == EPI_DLOGIT_ENT) {
+                    // coef d logp / d x_j + ecoef d H / d x_j,  d H / d x_j = -p_j (ln p_j + H),  ln p_j = x_j - lse
+                    bf16_t* cp = (bf16_t*)g.C + (long)m * g.ldc + n;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float d = round_bf(v[r]) - lse_m;
+                        float p = __expf(d);
+                        v[r] = coef_m * (((n + r) == tgt_m ? 1.f : 0.f) - p) - ecoef_m * p * (d + ent_m);
+                    }
+                    if (full) {
+                        u32x2 o; o.x = pack_bf2(v[0], v[1]); o.y = pack_bf2(v[2], v[3]);
+                        st8(cp, o);
+                    } else {
+                        for (int r = 0; r < 4; ++r) if (n + r < g.N) cp[r] = f2bf(v[r]);
+                    }
                 } else if (EPI == EPI_F32) {
                     float* cp = (float*)g.C + (long)m * g.ldc + n;
                     if (g.bias) {
@@ -318,7 +341,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4 (&acc)[4]
                 }
             }
         }
-    } else {  // EPI_LSE: each wave reduces its 64 columns per row
+    } else {  // EPI_LSE / EPI_LSE_ENT: each wave reduces its 64 columns per row
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {
             const int m = m0 + wm * 64 + mi * 16 + fr;
@@ -345,10 +368,18 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4 (&acc)[4]
             for (int i = 0; i < 16; ++i) s += (vals[i] > -1.0e38f) ? __expf(vals[i] - vmax) : 0.f;
             s += wave_shfl_xor(s, 16);
             s += wave_shfl_xor(s, 32);
+            float xs = 0.f;
+            if (EPI == EPI_LSE_ENT) {              // the exponentials of the sum above, each times its own exponent: every term <= 0
+#pragma unroll
+                for (int i = 0; i < 16; ++i) xs += (vals[i] > -1.0e38f) ? __expf(vals[i] - vmax) * (vals[i] - vmax) : 0.f;
+                xs += wave_shfl_xor(xs, 16);
+                xs += wave_shfl_xor(xs, 32);
+            }
             const int chunk = tile_n * 2 + wn;
             if (fq == 0 && m < g.M && chunk < g.nchunk) {
                 g.part_max[(long)m * g.nchunk + chunk] = vmax;
                 g.part_sum[(long)m * g.nchunk + chunk] = s;
+                if (EPI == EPI_LSE_ENT) g.part_xs[(long)m * g.nchunk + chunk] = xs;
             }
         }
     }
@@ -364,7 +395,7 @@ __device__ __forceinline__ void gemm_epilogue_w(const GemmArgs& g, f32x4 (&acc)[
     }
     const int fr = lane & 15, fq = lane >> 4;
     const float alpha = g.alpha;
-    if (EPI == EPI_LSE) {
+    if (EPI == EPI_LSE || EPI == EPI_LSE_ENT) {
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
             const int m = mw0 + mi * 16 + fr;
@@ -390,10 +421,18 @@ __device__ __forceinline__ void gemm_epilogue_w(const GemmArgs& g, f32x4 (&acc)[
             for (int i = 0; i < 16; ++i) s += (vals[i] > -1.0e38f) ? __expf(vals[i] - vmax) : 0.f;
             s += wave_shfl_xor(s, 16);
             s += wave_shfl_xor(s, 32);
+            float xs = 0.f;
+            if (EPI == EPI_LSE_ENT) {              // the exponentials of the sum above, each times its own exponent: every term <= 0
+#pragma unroll
+                for (int i = 0; i < 16; ++i) xs += (vals[i] > -1.0e38f) ? __expf(vals[i] - vmax) * (vals[i] - vmax) : 0.f;
+                xs += wave_shfl_xor(xs, 16);
+                xs += wave_shfl_xor(xs, 32);
+            }
             const int chunk = nw0 >> 6;
             if (fq == 0 && m < g.M && chunk < g.nchunk) {
                 g.part_max[(long)m * g.nchunk + chunk] = vmax;
                 g.part_sum[(long)m * g.nchunk + chunk] = s;
+                if (EPI == EPI_LSE_ENT) g.part_xs[(long)m * g.nchunk + chunk] = xs;
             }
         }
         return;
@@ -403,7 +442,9 @@ __device__ __forceinline__ void gemm_epilogue_w(const GemmArgs& g, f32x4 (&acc)[
         const int m = mw0 + mi * 16 + fr;
         if (m >= g.M) continue;
         float lse_m = 0.f, coef_m = 0.f; int tgt_m = -1;
-        if (EPI == EPI_DLOGIT) { lse_m = g.lse[m]; coef_m = g.coef[m]; tgt_m = g.tgt[m]; }
+        float ent_m = 0.f, ecoef_m = 0.f;
+        if (EPI == EPI_DLOGIT || EPI == EPI_DLOGIT_ENT) { lse_m = g.lse[m]; coef_m = g.coef[m]; tgt_m = g.tgt[m]; }
+        if (EPI == EPI_DLOGIT_ENT) { ent_m = g.ent[m]; ecoef_m = g.ecoef[m]; }
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
             const int n = nw0 + ni * 16 + fq * 4;
@@ -412,7 +453,7 @@ __device__ __forceinline__ void gemm_epilogue_w(const GemmArgs& g, f32x4 (&acc)[
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = acc[ni][mi][r] * alpha;
             const bool full = (n + 3 < g.N);
-            if (EPI == EPI_BF16 || EPI == EPI_DLOGIT) {
+            if (EPI == EPI_BF16 || EPI == EPI_DLOGIT || EPI == EPI_DLOGIT_ENT) {
                 if (EPI == EPI_BF16) {
                     if (g.bias) {
 #pragma unroll
@@ -428,11 +469,18 @@ __device__ __forceinline__ void gemm_epilogue_w(const GemmArgs& g, f32x4 (&acc)[
                                 if (n + r < g.N) v[r] = round_bf(v[r]) + bf2f(g.res[(long)m * g.ldres + n + r]);
                         }
                     }
-                } else {
+                } else if (EPI == EPI_DLOGIT) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         float p = __expf(round_bf(v[r]) - lse_m);
                         v[r] = coef_m * (((n + r) == tgt_m ? 1.f : 0.f) - p);
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float d = round_bf(v[r]) - lse_m;
+                        float p = __expf(d);
+                        v[r] = coef_m * (((n + r) == tgt_m ? 1.f : 0.f) - p) - ecoef_m * p * (d + ent_m);
                     }
                 }
                 bf16_t* cp = (bf16_t*)g.C + (long)m * g.ldc + n;
@@ -1761,4 +1809,35 @@ extern "C" int bra_lmhead_dlogits(const void* H, long ldh, const void* E, long l
     if (e) return e;
     if (!tgt || !lse || !coef || !dlogits || ldd % 4) return BRA_ERR_ARG;
     return dispatch_bk<EPI_DLOGIT>(g, (bra_stream_t)stream);
+}
+
+// bra_lmhead_lse_partials + the chunk's entropy partial part_xs (EPI_LSE_ENT): part_max / part_sum / tgt_logit are that entry point's bits
+extern "C" int bra_lmhead_lse_ent_partials(const void* H, long ldh, const void* E, long lde, int M, int V, int K,
+                                           const int* tgt, float* part_max, float* part_sum, float* part_xs,
+                                           float* tgt_logit, void* stream) {
+    GemmArgs g = {};
+    g.A = (const bf16_t*)H; g.lda = ldh; g.B = (const bf16_t*)E; g.ldb = lde;
+    g.M = M; g.N = V; g.K = K; g.alpha = 1.f;
+    g.tgt = tgt; g.part_max = part_max; g.part_sum = part_sum; g.part_xs = part_xs; g.tgt_logit = tgt_logit;
+    g.nchunk = (V + 63) / 64;
+    if (M == 0) return 0;
+    int e = check_common(g);
+    if (e) return e;
+    if (!tgt || !part_max || !part_sum || !part_xs || !tgt_logit) return BRA_ERR_ARG;
+    return dispatch_bk<EPI_LSE_ENT>(g, (bra_stream_t)stream);
+}
+
+// bra_lmhead_dlogits with the entropy's gradient in the same pass (EPI_DLOGIT_ENT)
+extern "C" int bra_lmhead_dlogits_ent(const void* H, long ldh, const void* E, long lde, int M, int V, int K,
+                                      const int* tgt, const float* lse, const float* coef, const float* ent,
+                                      const float* ecoef, void* dlogits, long ldd, void* stream) {
+    GemmArgs g = {};
+    g.A = (const bf16_t*)H; g.lda = ldh; g.B = (const bf16_t*)E; g.ldb = lde;
+    g.C = dlogits; g.ldc = ldd; g.M = M; g.N = V; g.K = K; g.alpha = 1.f;
+    g.tgt = tgt; g.lse = lse; g.coef = coef; g.ent = ent; g.ecoef = ecoef;
+    if (M == 0) return 0;
+    int e = check_common(g);
+    if (e) return e;
+    if (!tgt || !lse || !coef || !ent || !ecoef || !dlogits || ldd % 4) return BRA_ERR_ARG;
+    return dispatch_bk<EPI_DLOGIT_ENT>(g, (bra_stream_t)stream);
 }

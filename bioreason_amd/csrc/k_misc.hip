@@ -268,6 +268,37 @@ __global__ __launch_bounds__(256) void lse_merge_kernel(const float* part_max, c
     }
 }
 
+// the same merge with the row's entropy H = -sum_j p_j ln p_j from the third partial of EPI_LSE_ENT, part_xs_c = sum_j exp(x_j - max_c)
+// (x_j - max_c):  with w_c = exp(max_c - m),  T = sum_j exp(x_j - m) (x_j - m) = sum_c w_c (part_xs_c + (max_c - m) part_sum_c)  (every
+// term <= 0)  and  H = ln s - T / s  (both terms >= 0: no cancellation on a peaked row).  m, s, lse, logp: lse_merge_kernel's statements
+__global__ __launch_bounds__(256) void lse_ent_merge_kernel(const float* part_max, const float* part_sum, const float* part_xs,
+                                                            const float* tgt_logit, float* lse, float* logp, float* ent,
+                                                            int rows, int nchunk) {
+    const int row = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    const int lane = lane_id();
+    const bool live = row < rows;
+    const long base = (long)(live ? row : 0) * nchunk;
+    float m = -3.0e38f;
+    for (int c = lane; c < nchunk; c += 64) m = fmaxf(m, part_max[base + c]);
+    m = wave_max<64>(m);
+    float s = 0.f;
+    for (int c = lane; c < nchunk; c += 64) s += part_sum[base + c] * __expf(part_max[base + c] - m);
+    s = wave_sum<64>(s);
+    float t = 0.f;
+    for (int c = lane; c < nchunk; c += 64) {
+        const float d = part_max[base + c] - m;
+        t += __expf(d) * (part_xs[base + c] + d * part_sum[base + c]);
+    }
+    t = wave_sum<64>(t);
+    if (live && lane == 0) {
+        const float ls = __logf(s);
+        const float l = m + ls;
+        lse[row] = l;
+        if (logp) logp[row] = tgt_logit[row] - l;
+        ent[row] = fmaxf(ls - t / s, 0.f);
+    }
+}
+
 // fp32 <-> bf16 images of a flat gradient range: the optional bf16 transport of the data-parallel all-reduce (half the xGMI bytes of
 // the 148 MB fp32 arena; SURVEY section 8e "148 MB fp32 (or 74 MB bf16) bucket").  dir 0: dst(bf16) = round(src(f32)); 1: dst(f32) = src(bf16)
 __global__ __launch_bounds__(256) void cast_grad_kernel(const void* src, void* dst, long n, int dir) {
@@ -515,6 +546,15 @@ extern "C" int bra_lse_merge(const float* part_max, const float* part_sum, const
     if (!part_max || !part_sum || !lse || nchunk <= 0 || (logp && !tgt_logit)) return BRA_ERR_ARG;
     BRA_LAUNCH(lse_merge_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, part_max, part_sum, tgt_logit, lse,
                logp, rows, nchunk);
+    return BRA_LAUNCH_STATUS();
+}
+
+extern "C" int bra_lse_ent_merge(const float* part_max, const float* part_sum, const float* part_xs, const float* tgt_logit,
+                                 float* lse, float* logp, float* ent, int rows, int nchunk, void* stream) {
+    if (rows == 0) return 0;
+    if (!part_max || !part_sum || !part_xs || !lse || !ent || nchunk <= 0 || (logp && !tgt_logit)) return BRA_ERR_ARG;
+    BRA_LAUNCH(lse_ent_merge_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, part_max, part_sum, part_xs, tgt_logit, lse,
+               logp, ent, rows, nchunk);
     return BRA_LAUNCH_STATUS();
 }
 

@@ -21,8 +21,10 @@ def completion_mask(completion_ids: torch.Tensor, eos_token_id: int) -> torch.Te
 
 
 def per_token_logps(model, prompt_ids: torch.Tensor, prompt_mask: torch.Tensor, completion_ids: torch.Tensor,
-                    completion_mask_: torch.Tensor, **multimodal) -> torch.Tensor:
+                    completion_mask_: torch.Tensor, return_entropy: bool = False, **multimodal):
     """log pi(completion token | prefix) for every completion position -> fp32 [B, C].
+    `return_entropy`: -> (logp, ent), ent [B, C] the entropy of the policy's distribution at each of those positions (the bf16-rounded
+    logits at temperature 1, the distribution logp belongs to), from the same lm_head launches.
 
     Same quantity as `_get_per_token_logps(model, cat(prompt, completion), cat(masks))[:, P-1:]`
     (grpo_trainer.py:510-520 with the slice of :624/:640/:779), but the tied lm_head, the log-softmax and the
@@ -39,6 +41,9 @@ def per_token_logps(model, prompt_ids: torch.Tensor, prompt_mask: torch.Tensor, 
     rows = (torch.arange(B, device=dev, dtype=torch.int32)[:, None] * S
             + torch.arange(P - 1, S - 1, device=dev, dtype=torch.int32)[None, :]).reshape(-1).contiguous()
     tgt = completion_ids.to(torch.int32).reshape(-1).contiguous()
+    if return_entropy:
+        lp, ent = model.text_model.token_logprobs(hid, rows, tgt, return_entropy=True)
+        return lp.view(B, C), ent.view(B, C)
     return model.text_model.token_logprobs(hid, rows, tgt).view(B, C)
 
 
@@ -72,11 +77,31 @@ class _GrpoLossIsFn(torch.autograd.Function):
         return dlogp * g, None, None, None, None, None, None, None, None, None
 
 
-def grpo_loss(logp, old_logp, ref_logp, advantages, mask, epsilon_low=0.2, epsilon_high=0.2, beta=0.04, rollout_logp=None, is_cap=2.0):
+def _masked_row_mean(x, mask):
+    """mean_b( sum_c(x mask) / sum_c(mask) ): the reference's normalisation (grpo_trainer.py:801-803), statement for statement: a row without a live token is 0 / 0 there, in the loss kernel and here"""
+    mk = mask.to(x.dtype)
+    return ((x * mk).sum(1) / mk.sum(1)).mean()
+
+
+def grpo_loss(logp, old_logp, ref_logp, advantages, mask, epsilon_low=0.2, epsilon_high=0.2, beta=0.04, rollout_logp=None, is_cap=2.0,
+              entropy=None, entropy_coef=0.0):
     """-> (loss, stats[3] = {loss, mean_kl, clip_ratio}); old_logp=None <=> num_iterations == 1 (:786).
     `rollout_logp` fp32 [B, C] (generate(return_logprobs=True)): truncated importance sampling against the rollout's own policy — every
     token's policy-gradient term is weighted by min(pi_trainer / pi_rollout, is_cap), the weight a constant for the gradient
-    (bra_grpo_loss_is) -> (loss, stats[6] = {loss, mean_kl, clip_ratio, is_mean, is_capped, rollout_kl}).  None: the loss above."""
+    (bra_grpo_loss_is) -> (loss, stats[6] = {loss, mean_kl, clip_ratio, is_mean, is_capped, rollout_kl}).  None: the loss above.
+    `entropy` fp32 [B, C] (per_token_logps(return_entropy=True)): stats gains one trailing entry `entropy`, the masked per-row mean of
+    the policy's entropy averaged over the rows, and the loss is  loss - entropy_coef * that mean  — per_token_loss - entropy_coef H
+    under the reference's normalisation.  With entropy_coef == 0 the loss tensor is the one of before and the entropy receives no
+    gradient (stats[0] stays the kernel's loss, without the bonus)."""
+    if entropy is not None:
+        from .trainer import check_entropy_coef
+        entropy_coef = check_entropy_coef(entropy_coef)
+        loss, stats = grpo_loss(logp, old_logp, ref_logp, advantages, mask, epsilon_low, epsilon_high, beta, rollout_logp, is_cap)
+        h_mean = _masked_row_mean(entropy.float(), mask)
+        stats = torch.cat([stats, h_mean.detach().reshape(1)])
+        if entropy_coef != 0.0:
+            loss = loss - entropy_coef * h_mean
+        return loss, stats
     rl = ref_logp.contiguous() if (ref_logp is not None and beta != 0.0) else None
     ol = old_logp.contiguous() if old_logp is not None else None
     if rollout_logp is not None:
@@ -104,7 +129,8 @@ def repeat_sampler_indices(num_samples: int, mini_repeat_count: int, batch_size:
 
 
 def per_token_logps_shared_policy(model, prompt_ids: torch.Tensor, prompt_mask: torch.Tensor, completion_ids: torch.Tensor,
-                                  completion_mask_: torch.Tensor, prompt_alias: Sequence[int], side=None, **multimodal) -> Optional[torch.Tensor]:
+                                  completion_mask_: torch.Tensor, prompt_alias: Sequence[int], side=None, return_entropy: bool = False,
+                                  **multimodal):
     """`per_token_logps` WITH gradients (the policy pass of compute_loss, grpo_trainer.py:777-779) when the rows are groups of
     consecutive copies of a prompt (RepeatRandomSampler, :107-116): the prompt rows run once per distinct prompt — forward and
     backward — and the completion rows attend to [their prompt's K / V | their own].  Same log-probs as the full-sequence pass
@@ -113,7 +139,8 @@ def per_token_logps_shared_policy(model, prompt_ids: torch.Tensor, prompt_mask: 
     the chain rule gives for the sum of the copies' losses.  ~4.6x fewer rows than B x (P + C) at cfg-3.
     Deviation (stated in DESIGN.md): under LoRA dropout the shared prompt rows carry ONE mask stream for all copies of a prompt,
     the reference draws an independent mask per copy — the same marginal distribution per copy, correlated across the copies.
-    Returns None when the aliases are not uniform consecutive groups (the caller then runs `per_token_logps`)."""
+    Returns None when the aliases are not uniform consecutive groups (the caller then runs `per_token_logps`).
+    `return_entropy`: -> (logp, ent) as `per_token_logps` returns them."""
     from .generation import _uniform_groups
     grp = _uniform_groups(list(prompt_alias))
     if grp is None or grp[1] < 2:
@@ -128,11 +155,14 @@ def per_token_logps_shared_policy(model, prompt_ids: torch.Tensor, prompt_mask: 
                                   multimodal.get("dna_alias"), multimodal.get("dna_enc"))
     hid_last, hid_c = tm.hidden_states_shared(embeds.index_select(0, sel), prompt_mask.index_select(0, sel), completion_ids,
                                               completion_mask_, copies, side=side)
-    from .modeling import _ExpandGroupsFn, _LogProbFn
+    from .modeling import _ExpandGroupsFn, _LogProbEntFn, _LogProbFn
     H = hid_c.shape[-1]
     first = _ExpandGroupsFn.apply(hid_last, copies)                                          # [B, H]: predicts completion token 0
     hsel = torch.cat([first[:, None, :], hid_c.view(B, C, H)[:, : C - 1, :]], dim=1).reshape(B * C, H).contiguous()
     tgt = completion_ids.to(torch.int32).reshape(-1).contiguous()
+    if return_entropy:
+        lp, ent = _LogProbEntFn.apply(hsel, tm, tgt)
+        return lp.view(B, C), ent.view(B, C)
     return _LogProbFn.apply(hsel, tm, tgt).view(B, C)
 
 

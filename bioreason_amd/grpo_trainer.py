@@ -170,10 +170,20 @@ class DNALLMGRPOConfig(TrainingArguments):
     # policy-gradient term by min(pi_trainer / pi_rollout, cap), and is_mean / is_capped / rollout_kl are logged beside kl and clip_ratio
     rollout_is_correction: bool = field(default=False)
     rollout_is_cap: float = field(default=2.0)
+    # ---- not in the reference: the policy's per-token entropy from the fused lm_head pass (bioreason_amd.trainer.GRPOConfig.log_entropy /
+    # entropy_coef): log_entropy logs its masked mean as `entropy` beside kl and clip_ratio; entropy_coef > 0 (finite, >= 0; implies the
+    # metric) adds the bonus -entropy_coef * H to the per-token loss
+    log_entropy: bool = field(default=False)
+    entropy_coef: float = field(default=0.0)
     # ---- not in the reference: > 1 = `LengthBucketedRepeatSampler` — the global batches of a window of this many batches hold prompts of
     # similar expected cost (prompt + DNA length, refined by observed completion lengths), so the ranks of a step finish closer together
     # at the gather barrier; 1 (default) = the reference's RepeatRandomSampler, index for index
     length_bucket_batches: int = field(default=1)
+
+    def __post_init__(self):
+        from .trainer import check_entropy_coef
+        check_entropy_coef(self.entropy_coef)
+        super().__post_init__()
 
 
 def _lora_fields(peft_config) -> Optional[Dict[str, Any]]:
@@ -259,7 +269,8 @@ class DNALLMGRPOTrainer:
                          seed=args.seed, share_policy_prompt=getattr(args, "share_policy_prompt", None),
                          rollout_fp8=bool(getattr(args, "rollout_fp8", False)),
                          rollout_is_correction=bool(getattr(args, "rollout_is_correction", False)),
-                         rollout_is_cap=float(getattr(args, "rollout_is_cap", 2.0)))
+                         rollout_is_cap=float(getattr(args, "rollout_is_cap", 2.0)),
+                         log_entropy=bool(getattr(args, "log_entropy", False)), entropy_coef=getattr(args, "entropy_coef", 0.0))
         self.runner = GRPOStepRunner(model, cfg)
         self.state = SimpleNamespace(global_step=0, epoch=0.0, log_history=self.log_history)
         model.train()                                               # HF Trainer.training_step puts the model in train mode

@@ -191,6 +191,34 @@ class _LogProbFn(torch.autograd.Function):
         return dh, None, None
 
 
+class _LogProbEntFn(torch.autograd.Function):
+    """_LogProbFn plus the row's entropy H = -sum_j p_j ln p_j from the same two forward launches; the backward of both outputs is ONE
+    dlogits launch (coef = dlogp, ecoef = dent) and the one gemm_nt with E^T.  An entropy nobody differentiated (a metric) takes
+    _LogProbFn's dlogits call."""
+
+    @staticmethod
+    def forward(ctx, h, model, tgt):
+        eng = model.engine
+        logp, lse, ent = ops.lmhead_logprob_entropy(h, eng.E, tgt)
+        ctx.save_for_backward(h, tgt, lse, ent)
+        ctx.model = model
+        ctx.set_materialize_grads(False)
+        return logp, ent
+
+    @staticmethod
+    def backward(ctx, dlogp, dent):
+        h, tgt, lse, ent = ctx.saved_tensors
+        eng = ctx.model.engine
+        eng.ensure_transposed()
+        coef = dlogp.contiguous().float() if dlogp is not None else torch.zeros_like(lse)
+        if dent is None:
+            dlogits = ops.lmhead_dlogits(h, eng.E, tgt, lse, coef)
+        else:
+            dlogits = ops.lmhead_dlogits(h, eng.E, tgt, lse, coef, ent, dent.contiguous().float())
+        dh = ops.gemm_nt(dlogits, eng.ET[:, :eng.V] if eng.ET.shape[1] != eng.V else eng.ET)
+        return dh, None, None
+
+
 class _LogitsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, model):
@@ -517,9 +545,12 @@ class Qwen3ForCausalLM(nn.Module):
             logits = _LogitsFn.apply(hid, self).view(B, S, -1)
         return CausalLMOutputWithPast(loss=loss, logits=logits)
 
-    def token_logprobs(self, hid: torch.Tensor, rows: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
+    def token_logprobs(self, hid: torch.Tensor, rows: torch.Tensor, targets: torch.Tensor, return_entropy: bool = False):
         """log-probabilities of `targets` at hidden rows `rows` (int32) — the fused form of
-        `_get_per_token_logps` (grpo_trainer.py:510-520) restricted to the rows the caller keeps."""
+        `_get_per_token_logps` (grpo_trainer.py:510-520) restricted to the rows the caller keeps.
+        `return_entropy`: -> (logp, ent), ent the entropy of the same rows' distribution over the vocabulary (same launches)."""
+        if return_entropy:
+            return _LogProbEntFn.apply(_GatherRowsFn.apply(hid, rows), self, targets)
         return _LogProbFn.apply(_GatherRowsFn.apply(hid, rows), self, targets)
 
 

@@ -227,11 +227,42 @@ def lmhead_logprob(h: torch.Tensor, emb: torch.Tensor, tgt: torch.Tensor) -> Tup
     return logp, lse
 
 
-def lmhead_dlogits(h: torch.Tensor, emb: torch.Tensor, tgt: torch.Tensor, lse: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
+def lmhead_logprob_entropy(h: torch.Tensor, emb: torch.Tensor, tgt: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (logp[M], lse[M], ent[M]): `lmhead_logprob` plus the entropy H = -sum_j p_j ln p_j of softmax(h @ emb^T) (the bf16-rounded
+    logits at temperature 1: the distribution logp belongs to), in the same two launches — one more fp32 partial per (row, 64-column
+    chunk).  logp and lse are `lmhead_logprob`'s bits."""
+    M, K = h.shape
+    V = emb.shape[0]
+    nchunk = (V + 63) // 64
+    dev = h.device
+    pm = torch.empty((M, nchunk), dtype=torch.float32, device=dev)
+    ps = torch.empty((M, nchunk), dtype=torch.float32, device=dev)
+    px = torch.empty((M, nchunk), dtype=torch.float32, device=dev)
+    tl = torch.zeros((M,), dtype=torch.float32, device=dev)
+    lse = torch.empty((M,), dtype=torch.float32, device=dev)
+    logp = torch.empty((M,), dtype=torch.float32, device=dev)
+    ent = torch.empty((M,), dtype=torch.float32, device=dev)
+    st = current_stream(h)
+    lib = get_lib()
+    lib.call("bra_lmhead_lse_ent_partials", h, _ld(h), emb, _ld(emb), M, V, K, tgt, pm, ps, px, tl, st)
+    lib.call("bra_lse_ent_merge", pm, ps, px, tl, lse, logp, ent, M, nchunk, st)
+    return logp, lse, ent
+
+
+def lmhead_dlogits(h: torch.Tensor, emb: torch.Tensor, tgt: torch.Tensor, lse: torch.Tensor, coef: torch.Tensor,
+                   ent: Optional[torch.Tensor] = None, ecoef: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d (sum_m coef_m logp_m) / d logits, bf16 [M, V]; with `ent` (the rows' entropy, `lmhead_logprob_entropy`) and `ecoef`:
+    d (sum_m coef_m logp_m + ecoef_m H_m) / d logits in the same single launch"""
+    if (ent is None) != (ecoef is None):
+        raise ValueError("`ent` and `ecoef` go together: the entropy's gradient needs the rows' entropy and its coefficients")
     M, K = h.shape
     V = emb.shape[0]
     out = torch.empty((M, V), dtype=BF16, device=h.device)
-    get_lib().call("bra_lmhead_dlogits", h, _ld(h), emb, _ld(emb), M, V, K, tgt, lse, coef, out, _ld(out), current_stream(h))
+    if ecoef is None:
+        get_lib().call("bra_lmhead_dlogits", h, _ld(h), emb, _ld(emb), M, V, K, tgt, lse, coef, out, _ld(out), current_stream(h))
+    else:
+        get_lib().call("bra_lmhead_dlogits_ent", h, _ld(h), emb, _ld(emb), M, V, K, tgt, lse, coef, ent, ecoef, out, _ld(out),
+                       current_stream(h))
     return out
 
 

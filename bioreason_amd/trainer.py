@@ -86,6 +86,12 @@ class GRPOConfig:
     # together with the rollout's logits processors (the raw value of a drawn token is gone once they have edited the logits).
     rollout_is_correction: bool = False
     rollout_is_cap: float = 2.0
+    # opt-in: the policy's entropy H = -sum_j p_j ln p_j per completion token, taken in the policy pass's own lm_head launches (the
+    # bf16-rounded logits at temperature 1, whole vocabulary: the distribution the policy log-probs belong to).  log_entropy reports its
+    # masked mean as the metric `entropy`; entropy_coef > 0 (implies the metric) adds the bonus -entropy_coef * H to every token's loss
+    # under the loss's own normalisation, its gradient reaching the lm_head in the backward's one dlogits launch.
+    log_entropy: bool = False
+    entropy_coef: float = 0.0
     grad_buckets: int = 4
     # transport dtype of the gradient all-reduce: "fp32" (default: the flat arena itself, 148 MB) or "bf16" (each bucket is rounded to a
     # bf16 image, summed over the ranks in bf16 and widened back: half the xGMI bytes, one rounding per rank and per sum step — DDP's
@@ -106,6 +112,21 @@ class GRPOConfig:
     overlap_policy_chains: bool = True
     overlap_ref_chains: bool = False         # prompt / completion chains of the reference pass on two streams as well (measured: see NOTES)
     overlap_rollout_weights: bool = True     # merge + pack the rollout's weight set on a side stream beside the frozen DNA encoder
+
+    def __post_init__(self):
+        check_entropy_coef(self.entropy_coef)
+
+
+def check_entropy_coef(v) -> float:
+    """`entropy_coef` has to be a finite number >= 0 (a negative one would reward collapse)"""
+    import math
+    try:
+        f = float(v)                 # (a numpy scalar or a 0-dim tensor from a sweep script is a number too)
+    except (TypeError, ValueError):
+        f = math.nan
+    if isinstance(v, bool) or not math.isfinite(f) or f < 0:
+        raise ValueError(f"`entropy_coef` has to be finite and >= 0, but is {v!r}")
+    return f
 
 
 def token_stat_rewards(completion_ids: torch.Tensor, completion_mask: torch.Tensor) -> torch.Tensor:
@@ -301,6 +322,10 @@ class GRPOStepRunner(_DataParallelStep):
                 raise ValueError(f"`rollout_is_correction=True` cannot be combined with the rollout's logits processors ({', '.join(clash)}): "
                                  "the token loop cannot report the raw log-probability of a token drawn from processed logits")
             self.metric_names = list(self.metric_names) + ["is_mean", "is_capped", "rollout_kl"]
+        self.entropy_coef = check_entropy_coef(getattr(cfg, "entropy_coef", 0.0))
+        self.with_entropy = bool(getattr(cfg, "log_entropy", False)) or self.entropy_coef > 0.0
+        if self.with_entropy:
+            self.metric_names = list(self.metric_names) + ["entropy"]
         self.global_step = 0                # optimiser steps (HF: self.state.global_step)
         self._step = 0                      # forward/backward passes, incl. those inside an accumulation cycle (:395)
         self.step_idx = 0                   # rollouts generated (seeds the sampler)
@@ -457,14 +482,19 @@ class GRPOStepRunner(_DataParallelStep):
     def compute_loss(self, inputs: Dict):
         m, c = self.model, self.cfg
         lp = None
+        ekw = {"return_entropy": True} if self.with_entropy else {}          # (off: the calls of before, keyword for keyword)
         if self.shares_policy_prompt() and inputs.get("prompt_alias") is not None:
             side2 = self._side_stream(inputs["prompt_ids"].device, 1) if c.overlap_policy_chains else None
             lp = grpo.per_token_logps_shared_policy(m, inputs["prompt_ids"], inputs["prompt_mask"], inputs["completion_ids"],
-                                                    inputs["completion_mask"], inputs["prompt_alias"], side=side2,
+                                                    inputs["completion_mask"], inputs["prompt_alias"], side=side2, **ekw,
                                                     **inputs["multimodal_inputs"])
         if lp is None:
             lp = grpo.per_token_logps(m, inputs["prompt_ids"], inputs["prompt_mask"], inputs["completion_ids"],
-                                      inputs["completion_mask"], **inputs["multimodal_inputs"])
+                                      inputs["completion_mask"], **ekw, **inputs["multimodal_inputs"])
+        hkw = {}
+        if self.with_entropy:
+            lp, ent = lp
+            hkw = {"entropy": ent, "entropy_coef": self.entropy_coef}
         eps_hi = c.epsilon_high if c.epsilon_high is not None else c.epsilon
         old = inputs["old_per_token_logps"] if c.num_iterations > 1 else None          # :786
         if inputs.get("ref_join") is not None:                       # the reference pass ran beside the policy forward: join
@@ -472,9 +502,9 @@ class GRPOStepRunner(_DataParallelStep):
             inputs["ref_join"] = None
         if self.is_correction:
             return grpo.grpo_loss(lp, old, inputs["ref_per_token_logps"], inputs["advantages"], inputs["completion_mask"],
-                                  c.epsilon, eps_hi, c.beta, rollout_logp=inputs["rollout_per_token_logps"], is_cap=c.rollout_is_cap)
+                                  c.epsilon, eps_hi, c.beta, rollout_logp=inputs["rollout_per_token_logps"], is_cap=c.rollout_is_cap, **hkw)
         return grpo.grpo_loss(lp, old, inputs["ref_per_token_logps"], inputs["advantages"], inputs["completion_mask"],
-                              c.epsilon, eps_hi, c.beta)
+                              c.epsilon, eps_hi, c.beta, **hkw)
 
     def step(self, batch: Dict, timing: bool = False) -> Dict[str, torch.Tensor]:
         """one HF `training_step`: one forward/backward over one micro-batch; the optimiser runs when the accumulation cycle

@@ -103,6 +103,19 @@ int bra_lse_merge(const float* part_max, const float* part_sum, const float* tgt
 /* backward of the above: dlogits[m,n] = coef[m] * ((n == tgt[m]) - exp(logit[m,n] - lse[m]))  (bf16) */
 int bra_lmhead_dlogits(const void* H, long ldh, const void* E, long lde, int M, int V, int K, const int* tgt,
                        const float* lse, const float* coef, void* dlogits, long ldd, void* stream);
+/* The policy's entropy H[m] = -sum_j p_j ln p_j over the same bf16-rounded logits, in the same two launches: bra_lmhead_lse_partials
+ * plus part_xs[m, chunk] = sum_j exp(x_j - part_max) (x_j - part_max) (part_max / part_sum / tgt_logit are that entry point's bits), */
+int bra_lmhead_lse_ent_partials(const void* H, long ldh, const void* E, long lde, int M, int V, int K, const int* tgt,
+                                float* part_max, float* part_sum, float* part_xs, float* tgt_logit, void* stream);
+/* bra_lse_merge plus ent[m] = ln s - T / s,  T = sum_c exp(max_c - m) (part_xs_c + (max_c - m) part_sum_c)  (lse / logp are its bits;
+ * logp may be null), */
+int bra_lse_ent_merge(const float* part_max, const float* part_sum, const float* part_xs, const float* tgt_logit, float* lse,
+                      float* logp, float* ent, int rows, int nchunk, void* stream);
+/* and the backward of coef logp + ecoef H in one pass:
+ * dlogits[m,n] = coef[m] * ((n == tgt[m]) - p) - ecoef[m] * p * (logit[m,n] - lse[m] + ent[m]),  p = exp(logit[m,n] - lse[m])  (bf16) */
+int bra_lmhead_dlogits_ent(const void* H, long ldh, const void* E, long lde, int M, int V, int K, const int* tgt,
+                           const float* lse, const float* coef, const float* ent, const float* ecoef, void* dlogits, long ldd,
+                           void* stream);
 
 /* ---- normalisation / activation (k_norm.hip) --------------------------------- */
 /* Qwen3RMSNorm.forward (TF:qwen3:59-64); rstd (f32 [rows]) optional */
